@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Flagship benchmark: BERT-base seq=128, bs=8/GPU, Ok-Topk density=0.1%,
-bf16 autocast, synthetic data — the BASELINE.json headline config — plus an
-in-run dense-allreduce baseline for the speedup-vs-dense figure.
+bf16 autocast, synthetic data — the BASELINE.json headline config.  A plain
+run sets up, warms up, times the K steps and prints; `--full` adds the in-run
+dense-allreduce baseline for the speedup-vs-dense figure.
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`, launched
 under torch.distributed.run for N>1 (one rank per GPU over RCCL).  Rank 0
-prints ONE JSON line.
+prints ONE JSON line.  `--dump-outputs DIR` also writes the last timed step's
+loss, parameters and gradients as DIR/<name>.npy (seeded inputs: two runs
+with the same arguments start identically).
 """
 from __future__ import annotations
 
@@ -34,11 +37,54 @@ def parse_args():
                    help="round-2 load-balanced redistribution (equal AllGather blocks)")
     p.add_argument("--pipeline-chunks", type=int, default=1,
                    help="chunked engine pipeline (overlap comm with compress)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the in-run dense-allreduce baseline arm "
+                        "(dense_ms_per_step / speedup_vs_dense); a plain run "
+                        "times the headline steps only")
     p.add_argument("--dense-baseline-steps", type=int, default=-1,
-                   help="steps for the in-run dense baseline (-1: equal to "
-                        "--steps so the speedup figure compares like with "
-                        "like; 0: skip)")
+                   help="with --full: steps for the in-run dense baseline "
+                        "(-1: equal to --steps so the speedup figure compares "
+                        "like with like; 0: skip)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step "
+                        "left its caller (loss, model parameters, gradients) "
+                        "as DIR/<name>.npy, float32")
     return p.parse_args()
+
+
+# per dumped array: 4 Mi float32 = 16 MiB, so a dump stays well under 64 MB
+DUMP_MAX_ELEMS = 4 * 1024 * 1024
+
+
+def _sample_flat(tensors):
+    """Concatenate `tensors` flat and return them as a float32 numpy array;
+    above DUMP_MAX_ELEMS elements, a fixed seeded sample (sorted positions,
+    the same for every run with the same shapes)."""
+    flat = torch.cat([t.detach().reshape(-1) for t in tensors])
+    if flat.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(20240229)
+        idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g)
+        flat = flat[idx.sort().values.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(trainer, outdir):
+    """What a caller of trainer.step() holds after the last timed step: the
+    returned loss, the updated model parameters and the gradients left on
+    them, in model.parameters() order."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    params = [p for p in trainer.model.parameters() if p.requires_grad]
+    grads = [p.grad for p in params if p.grad is not None]
+    arrays = {
+        "loss": np.asarray([trainer.last_loss], dtype=np.float32),
+        "params": _sample_flat([p.data for p in params]),
+    }
+    if grads:
+        arrays["grads"] = _sample_flat(grads)
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), arr)
 
 
 def timed_steps(trainer, comm, steps):
@@ -110,6 +156,10 @@ def main():
     n_gpus = comm.size if comm.size > 1 else args.gpus
     rank = comm.rank
 
+    # same arguments -> same initial weights and dropout streams (the
+    # synthetic batches carry their own per-rank seed), so two builds can be
+    # compared output for output
+    torch.manual_seed(0)
     trainer = build_trainer(args, comm, args.compressor)
     for _ in range(max(args.warmup, 1)):
         trainer.step()
@@ -134,8 +184,11 @@ def main():
     phases = reducer_phase_ms(trainer, args.steps)
     comm_ms = sum(phases.get(p, 0.0) for p in ("alltoall", "allgather", "allreduce"))
     allreduce_ms = sum(phases.values())  # whole sparse-allreduce pipeline
+    if args.dump_outputs and rank == 0:
+        # before the --full arm below, which steps this trainer further
+        dump_outputs(trainer, args.dump_outputs)
 
-    dense_steps = args.dense_baseline_steps
+    dense_steps = args.dense_baseline_steps if args.full else 0
     if dense_steps < 0:
         # equal steps: at 8 GPUs RCCL warm-up effects make a short dense
         # arm noisy, and the headline speedup figure deserves a

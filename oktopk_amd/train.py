@@ -181,6 +181,12 @@ def main(argv=None) -> int:
                 logger.info("saved %s", path)
         comm.barrier()
     writer.close()
+    if runner is not None:
+        # join every heartbeat thread while rank 0's store server is still
+        # up: a daemon thread caught mid-store.set() against a vanished
+        # server during interpreter shutdown aborts the process
+        runner.agent.stop()
+        trainer.comm.barrier()
     return 0
 
 
