@@ -50,7 +50,9 @@ class BertEmbeddings(nn.Module):
         self.word_embeddings = nn.Embedding(cfg.vocab_size, cfg.hidden_size)
         self.position_embeddings = nn.Embedding(cfg.max_position_embeddings, cfg.hidden_size)
         self.token_type_embeddings = nn.Embedding(cfg.type_vocab_size, cfg.hidden_size)
-        self.ln = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
+        from ..ops.slot_ln import SlotLayerNorm
+
+        self.ln = SlotLayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
         self.dropout = nn.Dropout(cfg.hidden_dropout_prob)
 
     def forward(self, input_ids, token_type_ids=None):
@@ -109,13 +111,15 @@ class BertSelfAttention(nn.Module):
 class BertLayer(nn.Module):
     def __init__(self, cfg: BertConfig):
         super().__init__()
-        self.attn = BertSelfAttention(cfg)
-        self.ln1 = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
         from ..ops.fused_linear import ColsumLinear
+        from ..ops.slot_ln import SlotLayerNorm
+
+        self.attn = BertSelfAttention(cfg)
+        self.ln1 = SlotLayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
 
         self.fc1 = ColsumLinear(cfg.hidden_size, cfg.intermediate_size)
         self.fc2 = ColsumLinear(cfg.intermediate_size, cfg.hidden_size)
-        self.ln2 = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
+        self.ln2 = SlotLayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
         self.drop = nn.Dropout(cfg.hidden_dropout_prob)
 
     def forward(self, x, attn_mask=None):
@@ -151,7 +155,9 @@ class BertModel(nn.Module):
         self.cfg = cfg
         self.embeddings = BertEmbeddings(cfg)
         self.layer = nn.ModuleList(BertLayer(cfg) for _ in range(cfg.num_hidden_layers))
-        self.pooler = nn.Linear(cfg.hidden_size, cfg.hidden_size)
+        from ..ops.fused_linear import ColsumLinear
+
+        self.pooler = ColsumLinear(cfg.hidden_size, cfg.hidden_size)
         self.apply(self._init)
 
     def _init(self, m):
@@ -182,11 +188,32 @@ class BertForPreTraining(nn.Module):
 
     def __init__(self, cfg: BertConfig):
         super().__init__()
+        from ..ops.fused_linear import ColsumLinear, mark_every_backward
+        from ..ops.slot_ln import SlotLayerNorm, direct_ln_enabled
+
         self.bert = BertModel(cfg)
-        self.transform = nn.Linear(cfg.hidden_size, cfg.hidden_size)
-        self.transform_ln = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
+        self.transform = ColsumLinear(cfg.hidden_size, cfg.hidden_size)
+        self.transform_ln = SlotLayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
         self.decoder_bias = nn.Parameter(torch.zeros(cfg.vocab_size))
-        self.nsp = nn.Linear(cfg.hidden_size, 2)
+        self.nsp = ColsumLinear(cfg.hidden_size, 2)
+        # Every Linear of the pretraining model runs in every MLM+NSP
+        # backward, so an optimizer that aliases .grad into a flat buffer
+        # may let their backward write the slots directly and skip zeroing
+        # them (ops/fused_linear.py).  The tied decoder owns the
+        # word-embedding slot: its node overwrites it, the embedding
+        # lookup's gradient is added on top by autograd.  (A run that skips
+        # a head, e.g. no NSP labels, is caught by the optimizer's
+        # written-slot check and that head falls back to zero + accumulate.)
+        # The LayerNorms run in every backward too; their direct path is
+        # opt-in (OKTOPK_DIRECT_LN=1, ops/slot_ln.py).
+        direct_ln = direct_ln_enabled()
+        for m in self.modules():
+            if isinstance(m, ColsumLinear) or (direct_ln and isinstance(m, SlotLayerNorm)):
+                mark_every_backward(m.weight)
+                if m.bias is not None:
+                    mark_every_backward(m.bias)
+        mark_every_backward(self.decoder_bias)
+        mark_every_backward(self.bert.embeddings.word_embeddings.weight)
 
     def forward(
         self,
@@ -199,7 +226,10 @@ class BertForPreTraining(nn.Module):
         seq, pooled = self.bert(input_ids, token_type_ids, attention_mask)
         h = self.transform_ln(F.gelu(self.transform(seq)))
         # tied with word embeddings (reference ties decoder to embedding matrix)
-        logits = F.linear(h, self.bert.embeddings.word_embeddings.weight, self.decoder_bias)
+        from ..ops.fused_linear import direct_linear
+
+        logits = direct_linear(h, self.bert.embeddings.word_embeddings.weight,
+                               self.decoder_bias, w_shared=True)
         nsp_logits = self.nsp(pooled)
         if masked_lm_labels is None:
             return logits, nsp_logits

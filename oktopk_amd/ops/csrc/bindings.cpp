@@ -43,7 +43,14 @@ void launch_clip_scale(const double*, float, float*, hipStream_t);
 void launch_adam(float*, const float*, float*, float*, void*, const float*, int64_t, float, float,
                  float, float, float, hipStream_t);
 void launch_sumsq(const float*, int64_t, double*, hipStream_t);
-void launch_colsum_bf16(const void*, int64_t, int64_t, float*, hipStream_t);
+void launch_colsum_into_bf16(const void*, int64_t, int64_t, void*, int,
+                             hipStream_t);
+bool ln_bwd_supported(int64_t H);
+int ln_bwd_blocks(int64_t rows);
+void launch_ln_bwd_into(const void* gy, const void* x, const void* gamma,
+                        const float* mean, const float* rstd, int64_t rows,
+                        int64_t H, void* gx, float* ws, void* dgamma,
+                        void* dbeta, int accumulate, hipStream_t);
 void launch_attn_rowdot(const void*, const void*, int64_t, int64_t, int64_t,
                         float*, hipStream_t);
 void launch_linear_gelu(const void*, const void*, const float*, void*, void*, int,
@@ -459,18 +466,76 @@ static torch::Tensor grad_clip_scale(torch::Tensor t, double max_norm) {
     return out;
 }
 
-static torch::Tensor colsum_bf16(torch::Tensor gy) {
-    // bias gradient: sum over all leading dims of a bf16 [..., C] tensor,
-    // returned bf16 [C] (fp32 accumulation)
+static void colsum_bf16_into(torch::Tensor gy, torch::Tensor dst,
+                             bool accumulate) {
+    // bias gradient: dst[C] (=|+=) sum over all leading dims of a bf16
+    // [..., C] tensor.  One launch; fp32 accumulation, no atomics; dst may
+    // start at any element offset of a larger buffer.
     TORCH_CHECK(gy.is_cuda() && gy.scalar_type() == torch::kBFloat16 &&
-                gy.is_contiguous());
+                gy.is_contiguous() && gy.dim() >= 1, "gy: contiguous cuda bf16");
+    TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == torch::kBFloat16 &&
+                dst.is_contiguous() && dst.device() == gy.device(),
+                "dst: contiguous cuda bf16 on gy's device");
     int64_t C = gy.size(-1);
+    TORCH_CHECK(dst.numel() == C, "dst must hold gy.size(-1) elements");
+    if (C == 0) return;
     int64_t R = gy.numel() / C;
     const at::cuda::CUDAGuard guard(gy.device());
-    auto acc = torch::zeros({C}, gy.options().dtype(torch::kFloat32));
-    launch_colsum_bf16(gy.data_ptr(), R, C, acc.data_ptr<float>(),
-                       cur_stream());
-    return acc.to(torch::kBFloat16);
+    launch_colsum_into_bf16(gy.data_ptr(), R, C, dst.data_ptr(),
+                            accumulate ? 1 : 0, cur_stream());
+}
+
+static torch::Tensor linear_bwd_into(torch::Tensor gy, torch::Tensor x,
+                                     torch::Tensor w,
+                                     c10::optional<torch::Tensor> gw_dst,
+                                     c10::optional<torch::Tensor> gb_dst,
+                                     bool accumulate, bool bias_kernel) {
+    // backward of y = x W^T + b with the parameter gradients written
+    // straight into their slots: gW is the GEMM's own output (beta = 0, or
+    // beta = 1 when accumulating) and gb a column reduction whose output is
+    // the slot, so neither needs a temporary plus an add.  By default both
+    // leave exactly the bits autograd's zero + accumulate left; bias_kernel
+    // swaps torch's reduction for our one-launch column sum.  Returns gx.
+    TORCH_CHECK(gy.is_cuda() && gy.scalar_type() == torch::kBFloat16 &&
+                x.scalar_type() == torch::kBFloat16 &&
+                w.scalar_type() == torch::kBFloat16 && w.dim() == 2,
+                "linear_bwd_into: cuda bf16 operands");
+    const int64_t N = w.size(0), K = w.size(1);
+    TORCH_CHECK(gy.size(-1) == N && x.size(-1) == K &&
+                gy.numel() / std::max<int64_t>(N, 1) ==
+                    x.numel() / std::max<int64_t>(K, 1),
+                "linear_bwd_into: shape mismatch");
+    const at::cuda::CUDAGuard guard(gy.device());
+    at::NoGradGuard no_grad;
+    auto gy2 = gy.contiguous().view({-1, N});
+    auto x2 = x.reshape({-1, K});
+    auto gx = at::mm(gy2, w).view(x.sizes());
+    if (gw_dst.has_value()) {
+        auto& gw = *gw_dst;
+        TORCH_CHECK(gw.is_cuda() && gw.scalar_type() == torch::kBFloat16 &&
+                    gw.is_contiguous() && gw.dim() == 2 && gw.size(0) == N &&
+                    gw.size(1) == K, "gw_dst: contiguous bf16 [N, K]");
+        if (accumulate) gw.addmm_(gy2.t(), x2);
+        else at::mm_out(gw, gy2.t(), x2);
+    }
+    if (gb_dst.has_value()) {
+        auto& gb = *gb_dst;
+        if (bias_kernel) {
+            // one launch of ours; sums in another order than torch's
+            // reduction, so a rare element rounds to the neighbouring bf16
+            colsum_bf16_into(gy2, gb, accumulate);
+        } else {
+            // torch's own column reduction with the slot as its output:
+            // the bits autograd's `0 + sum` left there, minus the add
+            TORCH_CHECK(gb.is_cuda() && gb.scalar_type() == torch::kBFloat16 &&
+                        gb.is_contiguous() && gb.numel() == N,
+                        "gb_dst: contiguous bf16 [N]");
+            // accumulating: fp32 sum added in fp32, one rounding into the slot
+            if (accumulate) gb.add_(at::sum(gy2, {0}, false, at::kFloat));
+            else at::sum_out(gb, gy2, {0});
+        }
+    }
+    return gx;
 }
 
 static torch::Tensor attn_rowdot(torch::Tensor go, torch::Tensor out,
@@ -577,6 +642,46 @@ static std::vector<torch::Tensor> add_ln_bwd(torch::Tensor gy, torch::Tensor s,
                       gx.data_ptr(), dgamma.data_ptr<float>(),
                       dbeta.data_ptr<float>(), rows, H, cur_stream());
     return {gx, dgamma, dbeta};
+}
+
+static bool ln_bwd_into_supported(int64_t H) { return ln_bwd_supported(H); }
+
+static torch::Tensor ln_bwd_into(torch::Tensor gy, torch::Tensor x,
+                                 torch::Tensor gamma, torch::Tensor mean,
+                                 torch::Tensor rstd, torch::Tensor dgamma_dst,
+                                 torch::Tensor dbeta_dst, bool accumulate) {
+    // LayerNorm backward: returns gx; dgamma / dbeta are written (or
+    // accumulated) into their gradient slots.  Two launches, no zeroing.
+    TORCH_CHECK(gy.is_cuda() && gy.scalar_type() == torch::kBFloat16 &&
+                x.scalar_type() == torch::kBFloat16 &&
+                gamma.scalar_type() == torch::kBFloat16 &&
+                gy.sizes() == x.sizes(), "ln_bwd_into: cuda bf16, same shapes");
+    const int64_t H = x.size(-1);
+    TORCH_CHECK(ln_bwd_supported(H), "ln_bwd_into: unsupported hidden size ", H);
+    const int64_t rows = x.numel() / H;
+    TORCH_CHECK(gamma.numel() == H && gamma.is_contiguous());
+    for (auto* d : {&dgamma_dst, &dbeta_dst})
+        TORCH_CHECK(d->is_cuda() && d->scalar_type() == torch::kBFloat16 &&
+                    d->is_contiguous() && d->numel() == H,
+                    "ln_bwd_into: slots must be contiguous bf16 [H]");
+    TORCH_CHECK(mean.numel() == rows && rstd.numel() == rows);
+    const at::cuda::CUDAGuard guard(gy.device());
+    auto gyc = gy.contiguous();
+    auto xc = x.contiguous();
+    auto mf = mean.to(torch::kFloat32).contiguous();
+    auto rf = rstd.to(torch::kFloat32).contiguous();
+    TORCH_CHECK(((uintptr_t)gyc.data_ptr() & 3) == 0 &&
+                ((uintptr_t)xc.data_ptr() & 3) == 0, "ln_bwd_into: 4-byte alignment");
+    auto gx = torch::empty_like(xc);
+    if (rows == 0) return gx;
+    auto ws = torch::empty({(int64_t)ln_bwd_blocks(rows), 2 * H},
+                           gy.options().dtype(torch::kFloat32));
+    launch_ln_bwd_into(gyc.data_ptr(), xc.data_ptr(), gamma.data_ptr(),
+                       mf.data_ptr<float>(), rf.data_ptr<float>(), rows, H,
+                       gx.data_ptr(), ws.data_ptr<float>(),
+                       dgamma_dst.data_ptr(), dbeta_dst.data_ptr(),
+                       accumulate ? 1 : 0, cur_stream());
+    return gx;
 }
 
 static std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, torch::Tensor mask,
@@ -806,7 +911,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("grad_clip_scale", &grad_clip_scale,
           "device-resident clip factor min(1, max/||t||) (no host sync)");
     m.def("l2norm", &l2norm, "L2 norm (fp64 accumulate)");
-    m.def("colsum_bf16", &colsum_bf16, "bias grad: column sum of bf16 [R, C]");
+    m.def("colsum_bf16_into", &colsum_bf16_into,
+          "bias grad: dst (=|+=) column sum of bf16 [R, C], one launch",
+          py::arg("gy"), py::arg("dst"), py::arg("accumulate") = false);
+    m.def("ln_bwd_supported", &ln_bwd_into_supported,
+          "hidden sizes ln_bwd_into handles");
+    m.def("ln_bwd_into", &ln_bwd_into,
+          "LayerNorm backward; dgamma/dbeta written into their gradient slots, returns gx",
+          py::arg("gy"), py::arg("x"), py::arg("gamma"), py::arg("mean"),
+          py::arg("rstd"), py::arg("dgamma_dst"), py::arg("dbeta_dst"),
+          py::arg("accumulate") = false);
+    m.def("linear_bwd_into", &linear_bwd_into,
+          "Linear backward; gW/gb written into their gradient slots, returns gx",
+          py::arg("gy"), py::arg("x"), py::arg("w"), py::arg("gw_dst"),
+          py::arg("gb_dst"), py::arg("accumulate") = false,
+          py::arg("bias_kernel") = false);
     m.def("attn_rowdot", &attn_rowdot,
           "flash-bwd D: per-(head,row) dot of gO and O (head_dim 64)");
     m.def("sumsq_into_", &sumsq_into_,

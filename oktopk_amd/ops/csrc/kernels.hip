@@ -892,50 +892,10 @@ extern "C" void launch_sumsq(const float* t, int64_t n, double* out, hipStream_t
                        t, n, n4, out);
 }
 
-// ---------------------------------------------------------------------------
-// bias-grad column sum: gy bf16 [R, C] row-major -> out fp32 [C] (atomic
-// accumulate over row slabs; caller zeroes out).  Replaces torch's
-// per-linear reduce_kernel chain in backward (~10 us each, 9.9 us avg in
-// the r02-i profile) with a coalesced strip reduction.
-// ---------------------------------------------------------------------------
 __device__ __forceinline__ float ks_b2f(short u) {
     union { float f; uint32_t i; } c;
     c.i = ((uint32_t)(uint16_t)u) << 16;
     return c.f;
-}
-
-__global__ void colsum_bf16_kernel(const short* __restrict__ gy, int64_t R,
-                                   int64_t C, int64_t slab,
-                                   float* __restrict__ out) {
-    int64_t col = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (col >= C) return;
-    int64_t r0 = (int64_t)blockIdx.y * slab;
-    int64_t r1 = r0 + slab;
-    if (r1 > R) r1 = R;
-    // 4 independent partials keep 4 row loads in flight per thread
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int64_t r = r0;
-    for (; r + 4 <= r1; r += 4) {
-        a0 += ks_b2f(gy[r * C + col]);
-        a1 += ks_b2f(gy[(r + 1) * C + col]);
-        a2 += ks_b2f(gy[(r + 2) * C + col]);
-        a3 += ks_b2f(gy[(r + 3) * C + col]);
-    }
-    for (; r < r1; ++r) a0 += ks_b2f(gy[r * C + col]);
-    atomicAdd(&out[col], (a0 + a1) + (a2 + a3));
-}
-
-extern "C" void launch_colsum_bf16(const void* gy, int64_t R, int64_t C,
-                                   float* out, hipStream_t stream) {
-    // fill the chip: ~1024 blocks; column strips x row slabs
-    int64_t xblocks = (C + BLOCK - 1) / BLOCK;
-    int64_t target = 1024 / (xblocks ? xblocks : 1) + 1;
-    int64_t slab = (R + target - 1) / target;
-    if (slab < 8) slab = 8;
-    int64_t nslab = (R + slab - 1) / slab;
-    dim3 grid((unsigned)xblocks, (unsigned)nslab);
-    hipLaunchKernelGGL(colsum_bf16_kernel, grid, dim3(BLOCK), 0, stream,
-                       (const short*)gy, R, C, slab, out);
 }
 
 // ---------------------------------------------------------------------------

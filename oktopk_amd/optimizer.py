@@ -499,9 +499,105 @@ class FlatBertAdam:
             self.flat_param_model.copy_(self.flat_param)
         for p, (o, n_) in zip(self.params, self.slots):
             p.grad = self.flat_grad_model[o : o + n_].view_as(p)
+        self._bind_direct_grad()
+
+    # -- direct gradient slots -------------------------------------------
+    # A bound parameter's backward node (ops/fused_linear.py) writes the
+    # gradient into its slot instead of returning it, so the slot needs no
+    # zeroing and autograd runs no `slot += g` kernel for it.
+    #
+    # OWNERSHIP RULE: a slot is owned only if the module using the parameter
+    # runs in EVERY backward of the model — an owned slot is never zeroed,
+    # so a backward that skips its module would leave the previous step's
+    # gradient in it.  The model states that with mark_every_backward(); this
+    # optimizer binds only marked parameters, only on the bf16 GPU path, and
+    # only with OKTOPK_DIRECT_GRAD != 0.  As a guard the nodes record what
+    # they wrote: a parameter that an eager backward left unwritten (say the
+    # NSP head in a run without NSP labels) is zeroed, unbound and returned
+    # to the zero + accumulate path before its gradient is used.
+    _ZERO_MERGE_GAP = 1 << 16  # elements; see _plan_zero_ranges
+
+    def _bind_direct_grad(self) -> None:
+        from .ops.fused_linear import (GradSlotOwner, bind_grad_slot,
+                                       direct_grad_enabled, runs_every_backward)
+
+        self._dg_owner = None
+        self._dg_params: List[torch.Tensor] = []
+        self._zero_ranges: Optional[List[Tuple[int, int]]] = None
+        if not (direct_grad_enabled() and self.model_dtype == torch.bfloat16
+                and self.flat_grad_model.is_cuda):
+            return
+        owner = GradSlotOwner()
+        for p in self.params:
+            if runs_every_backward(p):
+                bind_grad_slot(p, p.grad, owner)
+                self._dg_params.append(p)
+        if self._dg_params:
+            self._dg_owner = owner
+            self._plan_zero_ranges()
+
+    def _plan_zero_ranges(self) -> None:
+        """Ranges of the flat buffer zero_grad() must fill: everything no
+        bound parameter owns (unrouted parameters, the alignment pad).
+        Neighbouring ranges separated by less than _ZERO_MERGE_GAP owned
+        elements are merged into one fill — zeroing an owned slot is
+        harmless (its node overwrites it) and a 128 KB fill is cheaper than
+        a second launch — which leaves BERT with two fills: the position +
+        token-type embeddings, and the bias/LayerNorm tail."""
+        bound = {id(p) for p in self._dg_params}
+        owned = sorted((o, o + n_) for p, (o, n_) in zip(self.params, self.slots)
+                       if id(p) in bound)
+        free, cur = [], 0
+        for a, b in owned:
+            if a > cur:
+                free.append([cur, a])
+            cur = max(cur, b)
+        if cur < self.numel:
+            free.append([cur, self.numel])
+        merged: List[List[int]] = []
+        for a, b in free:
+            if merged and a - merged[-1][1] < self._ZERO_MERGE_GAP:
+                merged[-1][1] = b
+            else:
+                merged.append([a, b])
+        self._zero_ranges = [(a, b) for a, b in merged]
+
+    def _settle_direct_grad(self) -> None:
+        """After an eager backward: any bound slot it did not write holds a
+        stale gradient — zero it and give the parameter back to the zero +
+        accumulate path.  Graph replays record nothing and skip this (the
+        captured backward is the one checked before capture)."""
+        owner = self._dg_owner
+        if owner is None or not owner.written:
+            return
+        from .ops.fused_linear import unbind_grad_slot
+
+        missing = [p for p in self._dg_params if id(p) not in owner.written]
+        owner.written.clear()
+        if missing:
+            gone = {id(p) for p in missing}
+            for p, (o, n_) in zip(self.params, self.slots):
+                if id(p) in gone:
+                    self.flat_grad_model[o : o + n_].zero_()
+                    unbind_grad_slot(p)
+            self._dg_params = [p for p in self._dg_params if id(p) not in gone]
+            self._plan_zero_ranges()
+
+    def set_substep(self, sub: int) -> None:
+        """Gradient-accumulation protocol (Trainer.step): sub-step 0 starts
+        a fresh accumulation, so every bound slot's next write overwrites;
+        in later sub-steps the nodes accumulate into what is there."""
+        if sub == 0 and self._dg_owner is not None:
+            self._settle_direct_grad()
+            self._dg_owner.written.clear()
 
     def zero_grad(self, set_to_none: bool = False):
-        self.flat_grad_model.zero_()
+        self._settle_direct_grad()
+        if self._zero_ranges is None:
+            self.flat_grad_model.zero_()
+        else:
+            for a, b in self._zero_ranges:
+                self.flat_grad_model[a:b].zero_()
         for p, (o, n_) in zip(self.params, self.slots):
             p.grad = self.flat_grad_model[o : o + n_].view_as(p)
 
@@ -523,6 +619,7 @@ class FlatBertAdam:
         return [self.current_lr()]
 
     def step(self):
+        self._settle_direct_grad()
         # 1. sparse allreduce of the whole flat gradient
         if self.cfg.compressor in ("dense", "none") and self.model_dtype != torch.float32:
             # dense baseline: allreduce the bf16 grads directly (half wire

@@ -403,6 +403,10 @@ class Trainer:
         for sub in range(self.nsteps_update):
             if hasattr(self.opt, "local"):
                 self.opt.local = sub < self.nsteps_update - 1
+            if hasattr(self.opt, "set_substep"):
+                # direct gradient slots: sub-step 0 overwrites, later ones
+                # accumulate (a captured graph is always sub-step 0)
+                self.opt.set_substep(sub)
             if self.autocast:
                 with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
                     loss = self._forward_loss()

@@ -28,11 +28,66 @@ def timeit(fn, iters=20, warmup=3):
     return (time.perf_counter() - t0) / iters
 
 
+def timeit_graph(fn, reps=100, replays=5):
+    """For microsecond-scale kernels: `reps` back-to-back calls captured
+    into one hipGraph, so the host's launch cost does not set the floor.
+    Seconds per call, kernel boundary (~1.5 us) included — what one such
+    kernel costs inside the captured fwd+bwd."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(reps):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(replays):
+        g.replay()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / (reps * replays)
+
+
+def colsum_rows():
+    """Bias-gradient column sum at the BERT-base shapes: the one-launch
+    kernel that stores into an (unaligned) gradient slot vs torch's sum(0)
+    into a preallocated output."""
+    g = torch.Generator().manual_seed(1)
+    rows = []
+    for C in (768, 3072, 30522):
+        gy = torch.randn(1024, C, generator=g).bfloat16().cuda()
+        dst = torch.empty(C + 8, dtype=torch.bfloat16, device="cuda")[3:3 + C]
+        out = torch.empty(C, dtype=torch.bfloat16, device="cuda")
+        nbytes = 2 * 1024 * C
+        for name, fn in (
+            (f"colsum_into [1024,{C}]", lambda: H.colsum_bf16_into(gy, dst, False)),
+            (f"torch sum(0) [1024,{C}]", lambda: torch.sum(gy, 0, out=out)),
+        ):
+            ms = timeit_graph(fn) * 1000
+            rows.append((name, ms, nbytes / GB / (ms / 1000)))
+    return rows
+
+
+def print_rows(rows):
+    print(f"{'op':28s} {'ms':>9s} {'GB/s':>8s}")
+    for name, ms, bw in rows:
+        print(f"{name:28s} {ms:9.4f} {bw:8.0f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--only", default="", choices=["", "colsum"],
+                    help="run just one group of rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.only == "colsum":
+        print_rows(colsum_rows())
+        return
     g = torch.Generator().manual_seed(0)
     t0 = torch.randn(N, generator=g).cuda()
     r0 = torch.randn(N, generator=g).cuda()
@@ -99,9 +154,8 @@ def main():
           lambda: H.scatter_gt_credit_(dest, r, idx, val, 0.0, 1.0),
           3 * 8 * idx.numel())
 
-    print(f"{'op':28s} {'ms':>9s} {'GB/s':>8s}")
-    for name, ms, bw in rows:
-        print(f"{name:28s} {ms:9.3f} {bw:8.0f}")
+    rows.extend(colsum_rows())
+    print_rows(rows)
 
 
 if __name__ == "__main__":
