@@ -297,6 +297,12 @@ class AllReducer:
             return torch.cat([idx.view(torch.int32), v.view(torch.int32)])
         return torch.cat([idx.view(torch.int32), val.view(torch.int32)])
 
+    def _pack_one(self, idx: torch.Tensor, val: torch.Tensor, n: int) -> torch.Tensor:
+        """_pack through the device wire codec (device_wire): one segment,
+        so the boundary table is just [0, n] and nothing is read back."""
+        return ops.pack_regions(idx, val, torch.tensor([0, n], dtype=torch.int64),
+                                self._wire_bf16)[0]
+
     def _unpack(self, buf: torch.Tensor, counts: List[int]) -> Tuple[torch.Tensor, torch.Tensor]:
         """Unpack rank-ordered packed segments; `counts` are ELEMENT counts
         per segment.  Values come back fp32."""
@@ -367,22 +373,29 @@ class AllReducer:
 
         s1 = time.perf_counter()
         if P > 1:
-            split_pts = torch.searchsorted(
-                idx.long(), bounds[1:P].to(idx.device)
-            ).cpu()
-            cuts = [0] + [int(x) for x in split_pts] + [sel]
-            elem_counts = [cuts[i + 1] - cuts[i] for i in range(P)]
-            # pack per destination: [idx | val bits] per region segment
-            segs = [self._pack(idx[cuts[i] : cuts[i + 1]], val[cuts[i] : cuts[i + 1]])
-                    for i in range(P)]
-            send = torch.cat(segs) if segs else idx.view(torch.int32)[:0]
+            if ok.device_wire:
+                # split + pack on the device: [idx | val bits] per region
+                # segment, same bytes as the host construction below
+                send, elem_counts = ops.pack_regions(idx, val, bounds,
+                                                     self._wire_bf16)
+            else:
+                split_pts = torch.searchsorted(
+                    idx.long(), bounds[1:P].to(idx.device)
+                ).cpu()
+                cuts = [0] + [int(x) for x in split_pts] + [sel]
+                elem_counts = [cuts[i + 1] - cuts[i] for i in range(P)]
+                # pack per destination: [idx | val bits] per region segment
+                segs = [self._pack(idx[cuts[i] : cuts[i + 1]], val[cuts[i] : cuts[i + 1]])
+                        for i in range(P)]
+                send = torch.cat(segs) if segs else idx.view(torch.int32)[:0]
             recv_elems = comm.alltoall_sizes(elem_counts, comm.device)
             recv = comm.alltoallv(
                 comm.to_comm(send),
                 [self._pack_ints(c) for c in elem_counts],
                 [self._pack_ints(c) for c in recv_elems],
             )
-            r_idx, r_val = self._unpack(recv, recv_elems)
+            if not ok.device_wire:
+                r_idx, r_val = self._unpack(recv, recv_elems)
         else:
             r_idx, r_val = idx, val
         self._time(name, "alltoall", time.perf_counter() - s1)
@@ -391,7 +404,12 @@ class AllReducer:
         exact = it % ok.global_threshold_recompute_interval == 0 or st.tau_global <= 0.0
         if P > 1:
             reduced = torch.zeros(hi - lo, dtype=t.dtype, device=t.device)
-            if r_idx.numel():
+            if ok.device_wire:
+                # fused unpack-reduce: the payload is never unpacked into
+                # r_idx / r_val / r_idx - lo temporaries
+                ops.unpack_scatter_add_(reduced, recv.to(t.device), recv_elems,
+                                        lo, self._wire_bf16)
+            elif r_idx.numel():
                 # int32 arithmetic keeps the wire dtype end-to-end (n < 2^31)
                 ops.scatter_add_(reduced, r_idx.to(t.device) - lo, r_val.to(t.device))
             self._time(name, "reduce", time.perf_counter() - s2)
@@ -432,6 +450,12 @@ class AllReducer:
             all_idx, all_val = gidx, gval
         elif ok.balanced_allgather:
             all_idx, all_val = self._balanced_round2(gidx, gval)
+        elif ok.device_wire:
+            pack = comm.to_comm(self._pack_one(gidx, gval, n))
+            elem_counts = [int(x) for x in comm.allgather_sizes(gidx.numel(), comm.device)]
+            buf, _ = comm.allgatherv(pack, sizes=[self._pack_ints(c) for c in elem_counts])
+            all_idx, all_val = ops.unpack_segments(buf.to(t.device), elem_counts,
+                                                   self._wire_bf16)
         else:
             pack = comm.to_comm(self._pack(gidx, gval))
             elem_counts = [int(x) for x in comm.allgather_sizes(gidx.numel(), comm.device)]
@@ -633,13 +657,18 @@ class AllReducer:
             self._repartition(st, idx, nl, c["it"])
             bounds = st.boundaries
             c["lo_r"], c["hi_r"] = int(bounds[rank]), int(bounds[rank + 1])
-            split_pts = torch.searchsorted(
-                idx.long(), bounds[1:P].to(idx.device)).cpu()
-            cuts = [0] + [int(x) for x in split_pts] + [idx.numel()]
-            c["elem_counts"] = [cuts[j + 1] - cuts[j] for j in range(P)]
-            segs = [self._pack(idx[cuts[j]:cuts[j + 1]],
-                               c["val"][cuts[j]:cuts[j + 1]]) for j in range(P)]
-            c["send"] = comm.to_comm(torch.cat(segs))
+            if ok.device_wire:
+                send, c["elem_counts"] = ops.pack_regions(
+                    idx, c["val"], bounds, self._wire_bf16)
+                c["send"] = comm.to_comm(send)
+            else:
+                split_pts = torch.searchsorted(
+                    idx.long(), bounds[1:P].to(idx.device)).cpu()
+                cuts = [0] + [int(x) for x in split_pts] + [idx.numel()]
+                c["elem_counts"] = [cuts[j + 1] - cuts[j] for j in range(P)]
+                segs = [self._pack(idx[cuts[j]:cuts[j + 1]],
+                                   c["val"][cuts[j]:cuts[j + 1]]) for j in range(P)]
+                c["send"] = comm.to_comm(torch.cat(segs))
             c["w_sizes"] = comm.alltoall_sizes_async(c["elem_counts"], comm.device)
         for c in parts:
             recv_elems = c["recv_elems"] = c["w_sizes"].wait()
@@ -653,10 +682,15 @@ class AllReducer:
         s2 = time.perf_counter()
         for c in parts:
             st = c["st"]
-            r_idx, r_val = self._unpack(c["w_payload"].wait(), c["recv_elems"])
+            recv = c["w_payload"].wait()
+            if not ok.device_wire:
+                r_idx, r_val = self._unpack(recv, c["recv_elems"])
             reduced = torch.zeros(c["hi_r"] - c["lo_r"],
                                   dtype=c["sl"].dtype, device=dev)
-            if r_idx.numel():
+            if ok.device_wire:
+                ops.unpack_scatter_add_(reduced, recv.to(dev), c["recv_elems"],
+                                        c["lo_r"], self._wire_bf16)
+            elif r_idx.numel():
                 ops.scatter_add_(reduced, r_idx.to(dev) - c["lo_r"],
                                  r_val.to(dev))
             exact = c["exact"] = (
@@ -668,7 +702,11 @@ class AllReducer:
             c["w_gsizes"] = comm.allgather_sizes_async(gidx.numel(), comm.device)
         for c in parts:
             sizes = c["gsizes"] = [int(x) for x in c["w_gsizes"].wait()]
-            pack = comm.to_comm(self._pack(c["gidx"], c["gval"]))
+            if ok.device_wire:
+                pack = comm.to_comm(
+                    self._pack_one(c["gidx"], c["gval"], c["sl"].numel()))
+            else:
+                pack = comm.to_comm(self._pack(c["gidx"], c["gval"]))
             c["w_gather"] = comm.allgatherv_async(
                 pack, [self._pack_ints(x) for x in sizes])
         self._time(label, "allgather", time.perf_counter() - s2)
@@ -677,9 +715,13 @@ class AllReducer:
         s4 = time.perf_counter()
         for c in parts:
             st, sl = c["st"], c["sl"]
-            all_idx, all_val = self._unpack(c["w_gather"].wait(), c["gsizes"])
-            all_idx = all_idx.to(dev)
-            all_val = all_val.to(dev)
+            if ok.device_wire:
+                all_idx, all_val = ops.unpack_segments(
+                    c["w_gather"].wait().to(dev), c["gsizes"], self._wire_bf16)
+            else:
+                all_idx, all_val = self._unpack(c["w_gather"].wait(), c["gsizes"])
+                all_idx = all_idx.to(dev)
+                all_val = all_val.to(dev)
             if c["exact"]:
                 kk = min(c["k"], all_val.numel())
                 if kk > 0:

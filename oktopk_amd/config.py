@@ -63,6 +63,16 @@ class OkTopkConfig:
     # P*max(s_r).  Pays when region survivor counts are skewed; the default
     # pad-to-max path is one collective fewer.
     balanced_allgather: bool = False
+    # Device-side wire codec: round 1 packs the per-destination segments
+    # with ops.pack_regions (two launches + the one count readback, in
+    # place of searchsorted + P slice-packs + cat), reduces the received
+    # payload with ops.unpack_scatter_add_ (one launch, nothing unpacked
+    # into temporaries), and round 2 unpacks with ops.unpack_segments.
+    # Same wire bytes as the host path.  Kernel-level timings against the
+    # host path are in profiles/README.md; whether it shortens a real
+    # multi-GPU step is unmeasured (default off; flip only after the
+    # multi-GPU win is measured).
+    device_wire: bool = False
 
 
 @dataclass

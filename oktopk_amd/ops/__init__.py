@@ -164,6 +164,45 @@ def scatter_gt_credit_(result, residual, idx, val, tau, scale=1.0) -> int:
         result, residual, idx, val, float(tau), float(scale)))
 
 
+# -- sparse wire codec ([idx int32 | val bits] per segment, fp32 or bf16) ---
+# The HIP kernels keep their segment tables in LDS and take a bounded number
+# of segments; beyond it the torch reference runs on the same device (a
+# world that large is far outside anything the kernels were sized for).
+
+def _wire_backend(t: torch.Tensor, nseg: int):
+    b = _backend(t)
+    if b is not _ref and nseg > b.wire_max_segments():
+        return _ref
+    return b
+
+
+def pack_regions(idx: torch.Tensor, val: torch.Tensor, bounds: torch.Tensor,
+                 wire_bf16: bool):
+    """Split the ascending selection at the [P+1] int64 CPU `bounds`
+    (segment j: bounds[j] <= idx < bounds[j+1]) and pack it into the wire
+    layout.  Returns (buf int32 on idx.device, counts: list of P ints)."""
+    buf, counts = _wire_backend(idx, bounds.numel() - 1).pack_regions(
+        idx, val, bounds, bool(wire_bf16))
+    return buf, [int(c) for c in counts]
+
+
+def unpack_segments(buf: torch.Tensor, counts, wire_bf16: bool):
+    """All wire segments gathered into contiguous (idx int32, val fp32)."""
+    counts = [int(c) for c in counts]
+    idx, val = _wire_backend(buf, len(counts)).unpack_segments(
+        buf, counts, bool(wire_bf16))
+    return idx, val
+
+
+def unpack_scatter_add_(dest: torch.Tensor, buf: torch.Tensor, counts,
+                        base: int, wire_bf16: bool) -> torch.Tensor:
+    """dest[idx - base] += val for every wire entry, without materialising
+    the unpacked segments (GPU).  base <= idx < base + dest.numel()."""
+    counts = [int(c) for c in counts]
+    return _wire_backend(dest, len(counts)).unpack_scatter_add_(
+        dest, buf, counts, int(base), bool(wire_bf16))
+
+
 def grad_clip_scale(t: torch.Tensor, max_norm: float) -> torch.Tensor:
     """Device-resident clip factor: min(1, max/(||t||+1e-6)) as a 1-elem
     tensor, no host sync (feeds fused_adam_'s gscale)."""

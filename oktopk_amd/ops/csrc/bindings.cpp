@@ -75,6 +75,16 @@ void launch_attn_bwd_fa(const void*, const void*, const void*, const void*,
                         const void*, void*, int, int, int, float, float,
                         unsigned long long, unsigned long long, const void*,
                         const void*, unsigned int, int, int, hipStream_t);
+// launchers from wire_codec.hip
+int wire_max_segments();
+void launch_wire_cuts(const int32_t*, int, const int64_t*, int, int, int*,
+                      hipStream_t);
+void launch_wire_pack(const int32_t*, const float*, int, const int*, int, int,
+                      int32_t*, hipStream_t);
+void launch_wire_unpack(const int32_t*, const int*, int, int, int, int32_t*,
+                        float*, hipStream_t);
+void launch_wire_scatter_add(float*, int64_t, const int32_t*, const int*, int,
+                             int, int64_t, int, hipStream_t);
 }
 
 namespace {
@@ -575,6 +585,126 @@ static double l2norm(torch::Tensor t) {
     return std::sqrt(out.cpu().item<double>());
 }
 
+// ---------------------------------------------------------------------------
+// sparse wire codec (wire_codec.hip): [idx int32 | val bits] per segment,
+// fp32 or bf16 values, segments in destination / rank order
+// ---------------------------------------------------------------------------
+static int64_t wire_words(int64_t c, bool bf16) {
+    return bf16 ? c + (c + 1) / 2 : 2 * c;
+}
+
+// [element prefix | word prefix] of `counts` as one device int32 tensor;
+// total elements / words come back through the out-params
+static torch::Tensor wire_tables(const std::vector<int64_t>& counts, bool bf16,
+                                 const torch::Tensor& like, int64_t* total_elems,
+                                 int64_t* total_words) {
+    const int64_t P = (int64_t)counts.size();
+    TORCH_CHECK(P <= wire_max_segments(), "wire codec: at most ",
+                wire_max_segments(), " segments, got ", P);
+    auto host = torch::empty({2 * (P + 1)}, torch::dtype(torch::kInt32));
+    int32_t* h = host.data_ptr<int32_t>();
+    int64_t e = 0, w = 0;
+    for (int64_t j = 0; j < P; ++j) {
+        TORCH_CHECK(counts[j] >= 0, "wire codec: negative segment count");
+        h[j] = (int32_t)e;
+        h[P + 1 + j] = (int32_t)w;
+        e += counts[j];
+        w += wire_words(counts[j], bf16);
+        TORCH_CHECK(w <= INT32_MAX, "wire codec: word count overflows int32");
+    }
+    h[P] = (int32_t)e;
+    h[2 * P + 1] = (int32_t)w;
+    *total_elems = e;
+    *total_words = w;
+    return host.to(like.device());
+}
+
+static std::tuple<torch::Tensor, std::vector<int64_t>> pack_regions(
+    torch::Tensor idx, torch::Tensor val, torch::Tensor bounds, bool wire_bf16) {
+    check_i32_1d(idx, "idx");
+    check_f32_1d(val, "val");
+    TORCH_CHECK(idx.numel() == val.numel(), "idx/val size mismatch");
+    TORCH_CHECK(bounds.device().is_cpu() && bounds.scalar_type() == torch::kInt64 &&
+                bounds.dim() == 1 && bounds.numel() >= 2 && bounds.is_contiguous(),
+                "bounds must be a contiguous int64 [P+1] CPU tensor");
+    const int64_t P = bounds.numel() - 1;
+    TORCH_CHECK(P <= wire_max_segments(), "wire codec: at most ",
+                wire_max_segments(), " segments, got ", P);
+    const int64_t* bp = bounds.data_ptr<int64_t>();
+    for (int64_t j = 0; j < P; ++j)
+        TORCH_CHECK(bp[j] <= bp[j + 1], "bounds must be non-decreasing");
+    const int64_t m = idx.numel();
+    // allocated before the counts are known: exact on the fp32 wire, the
+    // bound m + (m+P)/2 on the bf16 wire (at most P odd segments)
+    const int64_t cap = wire_bf16 ? m + (m + P) / 2 : 2 * m;
+    TORCH_CHECK(cap <= INT32_MAX, "wire codec: word count overflows int32");
+    const at::cuda::CUDAGuard guard(idx.device());
+    std::vector<int64_t> counts(P, 0);
+    if (m == 0)
+        return {torch::empty({0}, idx.options()), counts};
+    auto buf = torch::empty({cap}, idx.options());
+    auto meta = torch::empty({2 * (P + 1)}, idx.options());
+    torch::Tensor bdev;  // interior boundaries are only read when P > 1
+    if (P > 1) bdev = bounds.to(idx.device());
+    launch_wire_cuts(idx.data_ptr<int32_t>(), (int)m,
+                     P > 1 ? bdev.data_ptr<int64_t>() : nullptr, (int)P,
+                     wire_bf16 ? 1 : 0, meta.data_ptr<int>(), cur_stream());
+    launch_wire_pack(idx.data_ptr<int32_t>(), val.data_ptr<float>(), (int)m,
+                     meta.data_ptr<int>(), (int)P, wire_bf16 ? 1 : 0,
+                     buf.data_ptr<int32_t>(), cur_stream());
+    if (P == 1) {
+        counts[0] = m;  // nothing to read back
+    } else {
+        // the one host sync, after both launches are queued
+        auto ch = meta.narrow(0, 0, P + 1).cpu();
+        const int32_t* cp = ch.data_ptr<int32_t>();
+        for (int64_t j = 0; j < P; ++j) counts[j] = cp[j + 1] - cp[j];
+    }
+    int64_t words = 0;
+    for (int64_t j = 0; j < P; ++j) words += wire_words(counts[j], wire_bf16);
+    TORCH_CHECK(words <= cap, "wire codec: packed size exceeds its bound");
+    return {buf.narrow(0, 0, words), counts};
+}
+
+static std::vector<torch::Tensor> unpack_segments(torch::Tensor buf,
+                                                  std::vector<int64_t> counts,
+                                                  bool wire_bf16) {
+    check_i32_1d(buf, "buf");
+    const at::cuda::CUDAGuard guard(buf.device());
+    int64_t total = 0, words = 0;
+    auto meta = wire_tables(counts, wire_bf16, buf, &total, &words);
+    TORCH_CHECK(words <= buf.numel(), "wire codec: buf holds ", buf.numel(),
+                " words, counts need ", words);
+    auto out_idx = torch::empty({total}, buf.options());
+    auto out_val = torch::empty({total}, buf.options().dtype(torch::kFloat32));
+    if (total > 0)
+        launch_wire_unpack(buf.data_ptr<int32_t>(), meta.data_ptr<int>(),
+                           (int)counts.size(), (int)total, wire_bf16 ? 1 : 0,
+                           out_idx.data_ptr<int32_t>(), out_val.data_ptr<float>(),
+                           cur_stream());
+    return {out_idx, out_val};
+}
+
+static torch::Tensor unpack_scatter_add_(torch::Tensor dest, torch::Tensor buf,
+                                         std::vector<int64_t> counts,
+                                         int64_t base, bool wire_bf16) {
+    check_f32_1d(dest, "dest");
+    check_i32_1d(buf, "buf");
+    TORCH_CHECK(buf.device() == dest.device(), "buf must be on dest's device");
+    const at::cuda::CUDAGuard guard(dest.device());
+    int64_t total = 0, words = 0;
+    for (int64_t c : counts) total += c;
+    if (total == 0) return dest;
+    auto meta = wire_tables(counts, wire_bf16, buf, &total, &words);
+    TORCH_CHECK(words <= buf.numel(), "wire codec: buf holds ", buf.numel(),
+                " words, counts need ", words);
+    launch_wire_scatter_add(dest.data_ptr<float>(), dest.numel(),
+                            buf.data_ptr<int32_t>(), meta.data_ptr<int>(),
+                            (int)counts.size(), (int)total, base,
+                            wire_bf16 ? 1 : 0, cur_stream());
+    return dest;
+}
+
 static std::vector<torch::Tensor> linear_gelu(torch::Tensor x, torch::Tensor w,
                                               torch::Tensor bias, bool apply_gelu,
                                               bool want_pre) {
@@ -942,6 +1072,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("dropout_mask_mul_", &dropout_mask_mul_,
           "regenerate the forward's philox dropout mask in-place: "
           "a[i] = keep ? a[i]/keep_prob : 0");
+    m.def("wire_max_segments", []() { return (int64_t)wire_max_segments(); },
+          "largest segment count the wire codec kernels take");
+    m.def("pack_regions", &pack_regions,
+          "split an ascending (idx, val) selection at the region bounds and "
+          "pack it into the wire layout; returns (buf, counts)",
+          py::arg("idx"), py::arg("val"), py::arg("bounds"), py::arg("wire_bf16"));
+    m.def("unpack_segments", &unpack_segments,
+          "gather all wire segments into contiguous (idx int32, val fp32)",
+          py::arg("buf"), py::arg("counts"), py::arg("wire_bf16"));
+    m.def("unpack_scatter_add_", &unpack_scatter_add_,
+          "dest[idx - base] += val for every wire entry (fused unpack-reduce)",
+          py::arg("dest"), py::arg("buf"), py::arg("counts"), py::arg("base"),
+          py::arg("wire_bf16"));
     m.def("add_ln_fwd", &add_ln_fwd, "fused y=LN(x+r) forward (bf16)");
     m.def("add_ln_bwd", &add_ln_bwd, "fused add+LN backward (bf16, fp32 col sums)");
     m.def("linear_gelu", &linear_gelu,

@@ -31,6 +31,9 @@ __all__ = [
     "fused_sgd_",
     "fused_adam_",
     "l2norm",
+    "pack_regions",
+    "unpack_segments",
+    "unpack_scatter_add_",
 ]
 
 
@@ -211,6 +214,74 @@ def scatter_gt_credit_(result, residual, idx, val, tau, scale=1.0) -> int:
     result[j] = val[sel] * scale
     residual[j] = 0.0
     return int(sel.sum())
+
+
+# -- sparse wire codec ------------------------------------------------------
+# Wire layout (AllReducer._pack / _unpack / _pack_ints): segment j with c_j
+# elements is c_j int32 indices followed by the values — c_j fp32 words, or
+# ceil(c_j/2) int32 words of bf16 with a ZERO trailing half-word when c_j is
+# odd.  Segments are concatenated in destination / rank order.
+
+def _wire_words(c: int, wire_bf16: bool) -> int:
+    return c + (c + 1) // 2 if wire_bf16 else 2 * c
+
+
+def pack_regions(idx: torch.Tensor, val: torch.Tensor, bounds: torch.Tensor,
+                 wire_bf16: bool):
+    """Split the ascending selection (idx int32, val fp32) at the int64
+    [P+1] CPU boundary table and pack it: segment j holds the elements with
+    bounds[j] <= idx < bounds[j+1] (lower-bound rule — an index equal to a
+    boundary goes to the upper region).  Returns (buf int32, counts list).
+
+    Reference: the per-destination send buffers of the round-1 exchange,
+    VGG/allreducer.py:682-693."""
+    P = bounds.numel() - 1
+    m = idx.numel()
+    cuts = [0, m]
+    if P > 1:
+        split = torch.searchsorted(idx.long(), bounds[1:P].to(idx.device)).cpu()
+        cuts = [0] + [int(x) for x in split] + [m]
+    counts = [cuts[j + 1] - cuts[j] for j in range(P)]
+    segs = []
+    for j in range(P):
+        i, v = idx[cuts[j]:cuts[j + 1]], val[cuts[j]:cuts[j + 1]]
+        if wire_bf16:
+            v = v.to(torch.bfloat16)
+            if v.numel() % 2:
+                v = torch.cat([v, v.new_zeros(1)])
+        segs += [i.view(torch.int32), v.view(torch.int32)]
+    return torch.cat(segs), counts
+
+
+def unpack_segments(buf: torch.Tensor, counts, wire_bf16: bool):
+    """Gather rank-ordered wire segments into contiguous (idx int32, val
+    fp32); `counts` are ELEMENT counts per segment."""
+    idxs, vals = [], []
+    off = 0
+    for n in counts:
+        ints = _wire_words(n, wire_bf16)
+        idxs.append(buf[off:off + n])
+        if wire_bf16:
+            vals.append(buf[off + n:off + ints].view(torch.bfloat16)[:n].float())
+        else:
+            vals.append(buf[off + n:off + ints].view(torch.float32))
+        off += ints
+    if not idxs:
+        return buf[:0], buf[:0].view(torch.float32)
+    return torch.cat(idxs), torch.cat(vals)
+
+
+def unpack_scatter_add_(dest: torch.Tensor, buf: torch.Tensor, counts,
+                        base: int, wire_bf16: bool) -> torch.Tensor:
+    """dest[idx - base] += val over every wire entry (fused in HIP, which
+    never materialises idx / val).  The caller guarantees
+    base <= idx < base + dest.numel().
+
+    Reference: reduced_t[indexes - offset] += values, VGG/allreducer.py:779,794."""
+    idx, val = unpack_segments(buf, counts, wire_bf16)
+    if idx.numel():
+        scatter_add_(dest, idx - int(base), val)
+    return dest
 
 
 def grad_clip_scale(t: torch.Tensor, max_norm: float) -> torch.Tensor:

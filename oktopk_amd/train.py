@@ -46,6 +46,9 @@ def build_argparser() -> argparse.ArgumentParser:
                         "sigma-scale approximation is not needed")
     p.add_argument("--balanced-allgather", action="store_true",
                    help="oktopk round-2 load-balanced redistribution")
+    p.add_argument("--device-wire", action="store_true",
+                   help="oktopk device-side wire codec (region pack + fused "
+                        "unpack-reduce kernels)")
     p.add_argument("--pipeline-chunks", type=int, default=1,
                    help="chunked engine pipeline (docs/overlap_design.md)")
     p.add_argument("--dense-warmup", type=int, default=None,
@@ -90,6 +93,7 @@ def main(argv=None) -> int:
     overrides = dict(compressor=args.compressor, density=args.density,
                      profiling=args.profiling, profiling_norm=args.profiling_norm,
                      balanced_allgather=args.balanced_allgather,
+                     device_wire=args.device_wire,
                      pipeline_chunks=args.pipeline_chunks)
     if args.dense_warmup is not None:
         overrides["dense_warmup_iters"] = args.dense_warmup

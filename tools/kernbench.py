@@ -72,6 +72,100 @@ def colsum_rows():
     return rows
 
 
+def time_both(fn, iters, warmup=5):
+    """(device us, host wall us) per call over one window of `iters` calls.
+    Wall: host clock around the window, ending in a device synchronise.
+    Device: events bracketing the same window — the span the call occupies
+    on the GPU timeline, gaps where the device waits for the host's next
+    launch included (that is what a serial engine step pays)."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) / iters
+    return e0.elapsed_time(e1) * 1000 / iters, wall * 1e6
+
+
+def wire_rows(iters):
+    """Sparse wire codec (ops/csrc/wire_codec.hip) against the engine's host
+    path, same run, same inputs: m ~ 110k selected entries (BERT-base at
+    density 0.1%), P = 2 / 8 / 64 regions, fp32 and bf16 wire.
+
+      pack     ops.pack_regions  vs  searchsorted + .cpu() + P x _pack + cat
+      reduce   ops.unpack_scatter_add_  vs  _unpack + (idx - lo) + scatter_add_
+               (the payload one owner receives: P segments of ~m/P entries)
+      unpack   ops.unpack_segments  vs  _unpack   (round-2 allgather result)
+    Outputs of the two paths are compared before anything is timed."""
+    from oktopk_amd import AllReducer, Comm, EngineConfig, ops
+
+    n, m = 109_500_000, 110_000
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(0, n, (2 * m,), generator=g).unique()  # ascending
+    idx = idx[torch.randperm(idx.numel(), generator=g)[:m].sort().values]
+    idx = idx.to(torch.int32).cuda()
+    val = torch.randn(m, generator=g).cuda()
+    rows = []
+    for P in (2, 8, 64):
+        bounds = torch.tensor([i * (n // P) for i in range(P)] + [n],
+                              dtype=torch.int64)
+        for wire in ("fp32", "bf16"):
+            bf = wire == "bf16"
+            eng = AllReducer(Comm(None), EngineConfig(wire_dtype=wire))
+
+            def host_pack():
+                sp = torch.searchsorted(idx.long(), bounds[1:P].to(idx.device)).cpu()
+                cuts = [0] + [int(x) for x in sp] + [m]
+                return torch.cat([eng._pack(idx[cuts[i]:cuts[i + 1]],
+                                            val[cuts[i]:cuts[i + 1]])
+                                  for i in range(P)]), cuts
+
+            send, cuts = host_pack()
+            dsend, counts = ops.pack_regions(idx, val, bounds, bf)
+            assert torch.equal(send, dsend)
+            assert counts == [cuts[i + 1] - cuts[i] for i in range(P)]
+            # the payload the owner of region 0 receives: P senders' region-0
+            # segments (the same segment P times — duplicates hit every slot)
+            lo, hi = 0, int(bounds[1])
+            recv = send[:eng._pack_ints(counts[0])].repeat(P)
+            rc = [counts[0]] * P
+            reduced = torch.zeros(hi - lo, device="cuda")
+
+            def host_reduce():
+                r_idx, r_val = eng._unpack(recv, rc)
+                ops.scatter_add_(reduced, r_idx - lo, r_val)
+
+            a, b = eng._unpack(recv, rc)
+            c, d = ops.unpack_segments(recv, rc, bf)
+            assert torch.equal(a, c) and torch.equal(b, d)
+            # round-2 shape: P owners' survivor segments, ~m entries in all
+            gathered, gc = send, counts
+            for name, fn in (
+                (f"pack    host   P={P} {wire}", host_pack),
+                (f"pack    device P={P} {wire}",
+                 lambda: ops.pack_regions(idx, val, bounds, bf)),
+                (f"reduce  host   P={P} {wire}", host_reduce),
+                (f"reduce  device P={P} {wire}",
+                 lambda: ops.unpack_scatter_add_(reduced, recv, rc, lo, bf)),
+                (f"unpack  host   P={P} {wire}",
+                 lambda: eng._unpack(gathered, gc)),
+                (f"unpack  device P={P} {wire}",
+                 lambda: ops.unpack_segments(gathered, gc, bf)),
+            ):
+                dev_us, wall_us = time_both(fn, iters)
+                rows.append((name, dev_us, wall_us))
+    print(f"# wire codec, m={m} entries, index space n={n}, {iters} calls/row")
+    print(f"{'path':30s} {'device us':>10s} {'wall us':>10s}")
+    for name, dev_us, wall_us in rows:
+        print(f"{name:30s} {dev_us:10.1f} {wall_us:10.1f}")
+
+
 def print_rows(rows):
     print(f"{'op':28s} {'ms':>9s} {'GB/s':>8s}")
     for name, ms, bw in rows:
@@ -80,14 +174,20 @@ def print_rows(rows):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--only", default="", choices=["", "colsum"],
+    ap.add_argument("--iters", type=int, default=None,
+                    help="calls per timed window (default 20; 1000 for the "
+                         "microsecond-scale --only wire rows)")
+    ap.add_argument("--only", default="", choices=["", "colsum", "wire"],
                     help="run just one group of rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     if args.only == "colsum":
         print_rows(colsum_rows())
         return
+    if args.only == "wire":
+        wire_rows(args.iters or 1000)
+        return
+    args.iters = args.iters or 20
     g = torch.Generator().manual_seed(0)
     t0 = torch.randn(N, generator=g).cuda()
     r0 = torch.randn(N, generator=g).cuda()
