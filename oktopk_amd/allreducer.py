@@ -154,7 +154,9 @@ class AllReducer:
             return self._oktopk_chunked(name, tensor, grad_src)
         st = self.state(name, t)
         ok = self.cfg.oktopk
-        fused_ef = comp in ("oktopk", "topkAopt", "topkSA", "gaussiankSA")
+        fused_ef = comp in ("oktopk", "topkAopt", "topkSA", "gaussiankSA") or (
+            self.cfg.gaussian_device_select
+            and comp in ("gaussiank", "gaussiankconcat"))
         if grad_src is not None and not (
             fused_ef and st.counter >= ok.dense_warmup_iters
         ):
@@ -255,6 +257,18 @@ class AllReducer:
             st.grad_src = None
         else:
             ops.ef_restore_snapshot_(t, st.residual)
+
+    def _gaussian_select(self, t: torch.Tensor, st: TensorState, k: int):
+        """Device-resident Gaussian selection (gaussian_device_select): EF
+        restore (+ fused bf16 upcast of grad_src) snapshotted into
+        st.residual, threshold, refine walk and extraction in one op.  t is
+        NOT written — readers of the restored values use st.residual.
+        Returns (idx, val, tau)."""
+        grad = st.grad_src.reshape(-1) if st.grad_src is not None else None
+        st.grad_src = None
+        idx, val, _chosen, _cnt, tau, _tau0, _mean, _std = \
+            ops.gaussian_select_ef(t, st.residual, grad, self.cfg.density, k)
+        return idx, val, tau
 
     def get_current_density(self) -> float:
         """Per-epoch density schedule (reference get_current_density,
@@ -977,19 +991,25 @@ class AllReducer:
         k = self._k(n)
 
         s0 = time.perf_counter()
-        t.add_(st.residual)
-        tau = _gaussian_threshold(t, self.cfg.density)
-        # adaptive refinement (compression.py:236-255: 3 loops halving/growing)
-        for _ in range(3):
-            cnt = ops.count_gt(t, tau)
-            if cnt < 2 * k / 3:
-                tau *= 0.5
-            elif cnt > 4 * k / 3:
-                tau *= 1.5
-            else:
-                break
-        idx, val = ops.compact_gt(t, tau)
-        st.residual.copy_(t)
+        if self.cfg.gaussian_device_select:
+            # restore, threshold, refinement and extraction in one op; the
+            # restored values live in st.residual only (t is stale until
+            # the densify below overwrites it)
+            idx, val = self._gaussian_select(t, st, k)[:2]
+        else:
+            t.add_(st.residual)
+            tau = _gaussian_threshold(t, self.cfg.density)
+            # adaptive refinement (compression.py:236-255: 3 loops halving/growing)
+            for _ in range(3):
+                cnt = ops.count_gt(t, tau)
+                if cnt < 2 * k / 3:
+                    tau *= 0.5
+                elif cnt > 4 * k / 3:
+                    tau *= 1.5
+                else:
+                    break
+            idx, val = ops.compact_gt(t, tau)
+            st.residual.copy_(t)
         ops.zero_at_(st.residual, idx)
         self._time(name, "compress", time.perf_counter() - s0)
 
@@ -1026,18 +1046,24 @@ class AllReducer:
         k = self._k(n)
 
         s0 = time.perf_counter()
-        self._ef_restore(t, st)
-        tau = _gaussian_threshold(t, self.cfg.density)
-        for _ in range(3):
-            cnt = ops.count_gt(t, tau)
-            if cnt < 2 * k / 3:
-                tau *= 0.5
-            elif cnt > 4 * k / 3:
-                tau *= 1.5
-            else:
-                break
-        st.tau_local = tau
-        idx, val = ops.compact_gt(t, tau)  # index-sorted (compaction kernel)
+        if self.cfg.gaussian_device_select:
+            # t stays stale from here on: nothing below reads it before
+            # fill_sparse_scaled_ overwrites it with the result
+            idx, val, tau = self._gaussian_select(t, st, k)
+            st.tau_local = tau
+        else:
+            self._ef_restore(t, st)
+            tau = _gaussian_threshold(t, self.cfg.density)
+            for _ in range(3):
+                cnt = ops.count_gt(t, tau)
+                if cnt < 2 * k / 3:
+                    tau *= 0.5
+                elif cnt > 4 * k / 3:
+                    tau *= 1.5
+                else:
+                    break
+            st.tau_local = tau
+            idx, val = ops.compact_gt(t, tau)  # index-sorted (compaction kernel)
         bounds = self._uniform_boundaries(n)
         lo, hi = int(bounds[rank]), int(bounds[rank + 1])
         self._time(name, "compress", time.perf_counter() - s0)

@@ -92,6 +92,19 @@ class EngineConfig:
     # dtype used on the wire for sparse values ("fp32" | "bf16").
     wire_dtype: str = "fp32"
     oktopk: OkTopkConfig = field(default_factory=OkTopkConfig)
+    # Device-resident selection for gaussiank / gaussiankconcat /
+    # gaussiankSA: one ops.gaussian_select_ef call (EF restore with fused
+    # fp64 moments, on-device normal quantile, one 10-candidate count pass,
+    # on-device refine walk, compact write; one 48-byte readback) in place
+    # of the EF restore + torch mean/std + scipy ppf + up to three count_gt
+    # rounds + compact_gt (+ the residual copy of gaussiank).  With it on,
+    # gaussiank / gaussiankconcat also take the fused bf16 grad_src upcast.
+    # tau0 comes from fp64 moments rounded once to fp32, so tau can differ
+    # from the host path (fp32 moments, double tau) in the last bits — and
+    # the selection with it when an element sits exactly there.  Kernel-
+    # level timings against the host composition are in profiles/README.md;
+    # default off until a multi-GPU step time is measured.
+    gaussian_device_select: bool = False
     # EPS oracle (reference settings.PROFILING_NORM): when on, a dense
     # allreduce runs alongside the sparse one and the relative L2 error of the
     # sparse result is recorded.

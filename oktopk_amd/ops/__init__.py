@@ -96,6 +96,22 @@ def compact_adaptive_ef(t: torch.Tensor, residual: torch.Tensor,
     return idx, val, int(chosen), int(count)
 
 
+def gaussian_select_ef(t: torch.Tensor, residual: torch.Tensor, grad,
+                       density: float, k: int):
+    """Device-resident Gaussian-k selection: residual = float(grad)+residual
+    (or t+residual; t itself is NOT written), Gaussian-fit threshold from
+    fp64 moments, the three-round refine walk and the extraction at the
+    chosen threshold — three tensor-scale passes and one small readback on
+    the GPU.  Returns (idx, val, chosen, count, tau, tau0, mean, std) with
+    Python scalars; tau == float32(tau0 * GAUSS_FACTORS[chosen])."""
+    if grad is not None and grad.dtype != torch.bfloat16:
+        raise TypeError("gaussian_select_ef: grad must be bf16 (or None)")
+    idx, val, chosen, count, tau, tau0, mean, std = _backend(
+        t).gaussian_select_ef(t, residual, grad, float(density), int(k))
+    return (idx, val, int(chosen), int(count), float(tau), float(tau0),
+            float(mean), float(std))
+
+
 def scatter_add_(dest: torch.Tensor, idx: torch.Tensor, val: torch.Tensor) -> torch.Tensor:
     return _backend(dest).scatter_add_(dest, idx, val)
 

@@ -76,6 +76,15 @@ void launch_attn_bwd_fa(const void*, const void*, const void*, const void*,
                         unsigned long long, unsigned long long, const void*,
                         const void*, unsigned int, int, int, hipStream_t);
 // launchers from wire_codec.hip
+// gauss_select.hip
+void launch_gauss_moments(const float*, float*, const void*, int64_t, int64_t,
+                          int, double*, hipStream_t);
+void launch_gauss_finalize(const double*, int, int64_t, double, float*, double*,
+                           hipStream_t);
+void launch_gauss_count(const float*, int64_t, const float*, int64_t, int, int*,
+                        hipStream_t);
+void launch_gauss_decide(const int*, int, int64_t, const float*, double*,
+                         hipStream_t);
 int wire_max_segments();
 void launch_wire_cuts(const int32_t*, int, const int64_t*, int, int, int*,
                       hipStream_t);
@@ -271,6 +280,65 @@ static std::vector<torch::Tensor> compact_adaptive_ef(
     out.push_back(torch::tensor((int64_t)b.chosen));
     out.push_back(torch::tensor(b.total));
     return out;
+}
+
+// Device-resident Gaussian-k selection (gauss_select.hip): EF restore (+bf16
+// upcast) with fused fp64 moments, on-device normal quantile + candidate
+// table, one 10-candidate count pass, on-device refine-tree walk, then the
+// usual compact write from the residual snapshot.  One 48-byte readback.
+// Returns (idx, val, chosen, count, tau, tau0, mean, std).
+static std::tuple<torch::Tensor, torch::Tensor, int64_t, int64_t, double,
+                  double, double, double>
+gaussian_select_ef(torch::Tensor t, torch::Tensor residual,
+                   c10::optional<torch::Tensor> grad, double density,
+                   int64_t k) {
+    check_f32_1d(t, "t");
+    check_f32_1d(residual, "residual");
+    TORCH_CHECK(residual.numel() == t.numel(), "residual size mismatch");
+    TORCH_CHECK(density > 0.0 && density <= 1.0, "density must be in (0, 1]");
+    TORCH_CHECK(k >= 1, "k must be >= 1");
+    int64_t n = t.numel();
+    TORCH_CHECK(n >= 1, "gaussian_select_ef on empty tensor");
+    TORCH_CHECK(n < ((int64_t)1 << 31), "gaussian_select_ef needs n < 2^31");
+    const at::cuda::CUDAGuard guard(t.device());
+    const void* gp = nullptr;
+    if (grad.has_value()) {
+        auto& gt = grad.value();
+        TORCH_CHECK(gt.is_cuda() && gt.scalar_type() == torch::kBFloat16 &&
+                        gt.is_contiguous() && gt.numel() == n,
+                    "grad must be contiguous GPU bf16 of same numel");
+        gp = gt.data_ptr();
+    }
+    auto g = compact_geom(n);
+    const int nw = g.nblocks * 4;
+    auto f64 = t.options().dtype(torch::kFloat64);
+    auto partials = torch::empty({(int64_t)3 * nw}, f64);
+    auto rec = torch::empty({6}, f64);
+    auto cand = torch::empty({10}, t.options());
+    auto counts = torch::empty({(int64_t)10 * nw},
+                               t.options().dtype(torch::kInt32));
+    // upper-tail mass of the quantile 1 - density/2, formed the way the
+    // host path forms its ppf argument
+    const double q = 1.0 - (1.0 - density / 2.0);
+    auto stream = cur_stream();
+    launch_gauss_moments(t.data_ptr<float>(), residual.data_ptr<float>(), gp, n,
+                         g.chunk, g.nblocks, partials.data_ptr<double>(),
+                         stream);
+    launch_gauss_finalize(partials.data_ptr<double>(), nw, n, q,
+                          cand.data_ptr<float>(), rec.data_ptr<double>(),
+                          stream);
+    launch_gauss_count(residual.data_ptr<float>(), n, cand.data_ptr<float>(),
+                       g.chunk, g.nblocks, counts.data_ptr<int>(), stream);
+    launch_gauss_decide(counts.data_ptr<int>(), nw, k, cand.data_ptr<float>(),
+                        rec.data_ptr<double>(), stream);
+    auto rh = rec.cpu();
+    const double* rp = rh.data_ptr<double>();
+    int chosen = (int)rp[0];
+    int64_t total = (int64_t)rp[1];
+    double tau = rp[2];
+    auto out = compact_finish(residual, tau, g, counts, chosen, total);
+    return std::make_tuple(out[0], out[1], (int64_t)chosen, total, tau, rp[3],
+                           rp[4], rp[5]);
 }
 
 static double kth_abs_value(torch::Tensor t, int64_t k) {
@@ -1016,6 +1084,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fused EF restore(+bf16 upcast) + adaptive-threshold compaction",
           py::arg("t"), py::arg("residual"), py::arg("grad"), py::arg("taus"),
           py::arg("hi_limit"));
+    m.def("gaussian_select_ef", &gaussian_select_ef,
+          "device-resident Gaussian-k selection: EF restore + fp64 moments, "
+          "on-device ppf + refine tree, compact write; returns (idx, val, "
+          "chosen, count, tau, tau0, mean, std)",
+          py::arg("t"), py::arg("residual"), py::arg("grad"),
+          py::arg("density"), py::arg("k"));
     m.def("kth_abs_value", &kth_abs_value, "exact k-th largest |t| via radix select");
     m.def("scatter_add_", &scatter_add_, "dest[idx] += val");
     m.def("zero_at_", &zero_at_, "t[idx] = 0");

@@ -21,6 +21,7 @@ __all__ = [
     "count_gt",
     "count_multi_gt",
     "compact_adaptive",
+    "gaussian_select_ef",
     "scatter_add_",
     "zero_at_",
     "zero_at_masked_",
@@ -93,6 +94,76 @@ def compact_adaptive_ef(t: torch.Tensor, residual: torch.Tensor, grad,
     # steady state densifies the result into t without reading the
     # restored values — saving a full-tensor write on the GPU path
     return compact_adaptive(restored, taus, hi_limit)
+
+
+# every threshold the three-round refine loop of the gaussian compressors can
+# visit, as multiples of tau0: level l, h high moves -> 0.5^(l-h) * 1.5^h at
+# index l(l+1)/2 + h.  All factors are exact in binary.
+GAUSS_FACTORS = (1.0, 0.5, 1.5, 0.25, 0.75, 2.25, 0.125, 0.375, 1.125, 3.375)
+
+
+def gaussian_candidates(tau0: float) -> list:
+    """cand[j] = float32(double(tau0) * F[j]), as Python floats."""
+    t0 = float(torch.tensor(tau0, dtype=torch.float32))
+    return [float(torch.tensor(t0 * f, dtype=torch.float64).to(torch.float32))
+            for f in GAUSS_FACTORS]
+
+
+def gaussian_tree_walk(counts, k: int) -> int:
+    """Refine-tree walk over per-candidate counts (reference
+    VGG/compression.py:236-255 in integers): 3*cnt < 2k -> low child,
+    3*cnt > 4k -> high child, else stop; at most three counted rounds, the
+    candidate reached after the third move is not re-tested."""
+    l = h = 0
+    for _ in range(3):
+        cnt = int(counts[l * (l + 1) // 2 + h])
+        if 3 * cnt < 2 * k:
+            l += 1
+        elif 3 * cnt > 4 * k:
+            l += 1
+            h += 1
+        else:
+            break
+    return l * (l + 1) // 2 + h
+
+
+def gaussian_select_ef(t: torch.Tensor, residual: torch.Tensor, grad,
+                       density: float, k: int):
+    """Torch oracle of the device-resident Gaussian-k selection: EF restore
+    (with optional bf16 grad upcast) snapshotted into `residual` (t is NOT
+    written, as in compact_adaptive_ef), Gaussian-fit threshold from fp64
+    moments (reference utils.gen_threshold_from_normal_distribution,
+    VGG/utils.py:136-138), the refine loop of VGG/compression.py:236-255
+    over the float32 candidate table, and extraction at the chosen candidate.
+    Returns (idx, val, chosen, count, tau, tau0, mean, std)."""
+    import math
+
+    if not (0.0 < density <= 1.0):
+        raise ValueError("density must be in (0, 1]")
+    if k < 1 or t.numel() < 1 or residual.numel() != t.numel():
+        raise ValueError("gaussian_select_ef: bad k or sizes")
+    if grad is not None:
+        restored = grad.reshape(-1).to(t.dtype) + residual
+    else:
+        restored = t + residual
+    residual.copy_(restored)
+    v = restored.double()
+    n = v.numel()
+    mean = float(v.mean().item())
+    std = float(v.std().item()) if n > 1 else 0.0
+    if n < 2 or not math.isfinite(std) or std == 0.0:
+        tau0d = abs(mean)
+    else:
+        z = float(torch.special.ndtri(
+            torch.tensor(1.0 - density / 2.0, dtype=torch.float64)).item())
+        tau0d = abs(mean + std * z)
+    tau0 = float(torch.tensor(tau0d, dtype=torch.float64).to(torch.float32))
+    cand = gaussian_candidates(tau0)
+    counts = count_multi_gt(restored, cand)
+    chosen = gaussian_tree_walk(counts, int(k))
+    tau = cand[chosen]
+    idx, val = compact_gt(restored, tau)
+    return idx, val, chosen, counts[chosen], tau, tau0, mean, std
 
 
 def scatter_add_(dest: torch.Tensor, idx: torch.Tensor, val: torch.Tensor) -> torch.Tensor:

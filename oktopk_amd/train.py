@@ -49,6 +49,10 @@ def build_argparser() -> argparse.ArgumentParser:
     p.add_argument("--device-wire", action="store_true",
                    help="oktopk device-side wire codec (region pack + fused "
                         "unpack-reduce kernels)")
+    p.add_argument("--gaussian-device-select", action="store_true",
+                   help="gaussiank/gaussiankconcat/gaussiankSA: device-"
+                        "resident threshold selection (fused moments + ppf "
+                        "+ refine kernels) instead of the host loop")
     p.add_argument("--pipeline-chunks", type=int, default=1,
                    help="chunked engine pipeline (docs/overlap_design.md)")
     p.add_argument("--dense-warmup", type=int, default=None,
@@ -94,6 +98,7 @@ def main(argv=None) -> int:
                      profiling=args.profiling, profiling_norm=args.profiling_norm,
                      balanced_allgather=args.balanced_allgather,
                      device_wire=args.device_wire,
+                     gaussian_device_select=args.gaussian_device_select,
                      pipeline_chunks=args.pipeline_chunks)
     if args.dense_warmup is not None:
         overrides["dense_warmup_iters"] = args.dense_warmup

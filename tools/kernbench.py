@@ -166,6 +166,76 @@ def wire_rows(iters):
         print(f"{name:30s} {dev_us:10.1f} {wall_us:10.1f}")
 
 
+def gauss_rows(reps, sizes=(109_500_000, 25_000_000), density=0.001,
+               device="cuda"):
+    """Device-resident Gaussian-k selection (ops.gaussian_select_ef,
+    ops/csrc/gauss_select.hip) against the host composition the gaussiank
+    engine path runs without it: ef_restore_snapshot_ + _gaussian_threshold
+    (torch mean/std + scipy ppf) + the three-round count_gt loop +
+    compact_gt + residual.copy_.  Inputs: randn (the loop stops at round 1)
+    and randn**3 (all three rounds).  Both paths end in a host readback, so
+    each call is timed alone: reset inputs, synchronise, host clock around
+    call + synchronise.  The two paths alternate inside one repeat loop;
+    median and min..max over `reps` repeats."""
+    from oktopk_amd import ops
+    from oktopk_amd.allreducer import _gaussian_threshold
+
+    def sync():
+        if device != "cpu":
+            torch.cuda.synchronize()
+
+    print(f"# gaussian select, density={density}, {reps} repeats/row")
+    print(f"{'path':34s} {'median ms':>10s} {'min ms':>9s} {'max ms':>9s}")
+    for n in sizes:
+        k = max(1, int(n * density))
+        g = torch.Generator().manual_seed(0)
+        x = torch.randn(n, generator=g)
+        r0 = (torch.randn(n, generator=g) * 0.01).to(device)
+        for label, t0 in (("randn", x.to(device)), ("randn**3", (x ** 3).to(device))):
+            t, r = t0.clone(), r0.clone()
+
+            def host():
+                ops.ef_restore_snapshot_(t, r)
+                tau = _gaussian_threshold(t, density)
+                for _ in range(3):
+                    cnt = ops.count_gt(t, tau)
+                    if cnt < 2 * k / 3:
+                        tau *= 0.5
+                    elif cnt > 4 * k / 3:
+                        tau *= 1.5
+                    else:
+                        break
+                idx, val = ops.compact_gt(t, tau)
+                r.copy_(t)
+                return idx, tau
+
+            def dev():
+                out = ops.gaussian_select_ef(t, r, None, density, k)
+                return out[0], out[4]
+
+            times = {"host": [], "device": []}
+            sel = {}
+            for rep in range(reps + 2):  # two warm-up repeats
+                for name, fn in (("host", host), ("device", dev)):
+                    t.copy_(t0)
+                    r.copy_(r0)
+                    sync()
+                    c0 = time.perf_counter()
+                    idx, tau = fn()
+                    sync()
+                    if rep >= 2:
+                        times[name].append((time.perf_counter() - c0) * 1000)
+                    sel[name] = (idx.numel(), tau)
+            # same decision (tau may differ in the last bits: fp32 vs fp64
+            # moments), so the selected counts agree to a few elements
+            assert abs(sel["host"][1] - sel["device"][1]) <= 1e-4 * sel["host"][1], sel
+            assert abs(sel["host"][0] - sel["device"][0]) <= 0.01 * k + 2, sel
+            for name in ("host", "device"):
+                ts = sorted(times[name])
+                print(f"{name:6s} {label:9s} n={n:<11d} sel={sel[name][0]:<8d}"
+                      f"{ts[len(ts) // 2]:10.3f} {ts[0]:9.3f} {ts[-1]:9.3f}")
+
+
 def print_rows(rows):
     print(f"{'op':28s} {'ms':>9s} {'GB/s':>8s}")
     for name, ms, bw in rows:
@@ -176,8 +246,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=None,
                     help="calls per timed window (default 20; 1000 for the "
-                         "microsecond-scale --only wire rows)")
-    ap.add_argument("--only", default="", choices=["", "colsum", "wire"],
+                         "microsecond-scale --only wire rows; repeats per "
+                         "row, default 15, for --only gauss)")
+    ap.add_argument("--only", default="", choices=["", "colsum", "wire", "gauss"],
                     help="run just one group of rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -186,6 +257,9 @@ def main():
         return
     if args.only == "wire":
         wire_rows(args.iters or 1000)
+        return
+    if args.only == "gauss":
+        gauss_rows(args.iters or 15)
         return
     args.iters = args.iters or 20
     g = torch.Generator().manual_seed(0)
