@@ -86,6 +86,20 @@ class TensorState:
         self.boundaries = d["boundaries"]
 
 
+@dataclass
+class SparseGrad:
+    """The reduced gradient in sparse form (run(..., sparse_ok=True)): the
+    dense result is val[i]*scale at idx[i] where |val[i]| > tau (tau < 0
+    keeps every entry) and +0.0 elsewhere.  idx is int32, ascending and
+    unique — the layout ops.grad_clip_scale_sparse / fused_adam_sparse_
+    consume without the dense buffer ever being filled."""
+
+    idx: torch.Tensor
+    val: torch.Tensor
+    scale: float
+    tau: float
+
+
 class AllReducer:
     """Synchronous whole-tensor sparse allreduce (the BERT-variant surface,
     BERT/bert/allreducer.py:181,347).  The bucketed/overlapped mode used by
@@ -112,6 +126,10 @@ class AllReducer:
         # hook-driven overlap path leaves it False (a sync per bucket would
         # destroy backward/compress overlap).
         self.timing_sync = False
+        # sparse hand-over (run(..., sparse_ok=True)): the last run's result
+        # as a SparseGrad, or None when that run densified as usual
+        self.sparse_result: Optional[SparseGrad] = None
+        self._sparse_ok = False
 
     def set_comm(self, comm: Comm) -> None:
         """Swap the communicator after an elastic shrink; per-world state
@@ -134,12 +152,19 @@ class AllReducer:
 
     # ------------------------------------------------------------------
     def run(self, name: str, tensor: torch.Tensor,
-            grad_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+            grad_src: Optional[torch.Tensor] = None,
+            sparse_ok: bool = False) -> torch.Tensor:
         """Sparse-allreduce `tensor` (1-D fp32 grad) in place; returns it.
 
         `grad_src` (optional, bf16): raw model-dtype gradient; the upcast
         into `tensor` is fused with the error-feedback restore where the
         compressor path supports it (one streaming pass saved).
+
+        `sparse_ok`: the caller can consume a SparseGrad.  Where the path
+        taken ends in an ascending selection (the non-exact Ok-Topk tails)
+        the result is then left in `self.sparse_result` and `tensor` is NOT
+        written — no zero fill, no scatter; every other path densifies as
+        usual and leaves `self.sparse_result` None for that step.
 
         The result equals (approximately, by global-top-k truncation) the
         dense mean gradient over all ranks.
@@ -148,6 +173,9 @@ class AllReducer:
         if self.timing_sync and t.is_cuda:
             torch.cuda.synchronize()
         comp = self.cfg.compressor
+        self.sparse_result = None
+        # profiling_norm compares the dense result against the oracle
+        self._sparse_ok = bool(sparse_ok) and not self.cfg.profiling_norm
         if comp == "oktopk" and self.cfg.oktopk.pipeline_chunks > 1:
             # chunked stage-interleaved engine keeps per-chunk states and
             # skips the full-tensor state below (docs/overlap_design.md)
@@ -448,9 +476,18 @@ class AllReducer:
                 # feedback controller (replaces nonzero() + two gathers +
                 # fill + masked credit)
                 result = t
-                result.zero_()
-                gsz = ops.scatter_gt_credit_(result, st.residual, idx, val,
-                                             st.tau_global, 1.0)
+                if self._sparse_ok:
+                    # sparse hand-over: the unfiltered local selection plus
+                    # tau_global IS the result (idx ascending: compaction
+                    # order) — credit and count only, t stays unwritten
+                    self.sparse_result = SparseGrad(idx, val, 1.0,
+                                                    st.tau_global)
+                    gsz = ops.scatter_gt_credit_(None, st.residual, idx, val,
+                                                 st.tau_global)
+                else:
+                    result.zero_()
+                    gsz = ops.scatter_gt_credit_(result, st.residual, idx,
+                                                 val, st.tau_global, 1.0)
                 if gsz < ok.global_lo_num * k // ok.global_lo_den:
                     st.tau_global /= ok.scale_global_increase
                 elif gsz > ok.global_hi_num * k // ok.global_hi_den:
@@ -503,7 +540,17 @@ class AllReducer:
 
         # --- 5. densify result + residual credit -------------------------
         result = t  # reuse the gradient storage, reference VGG/allreducer.py:838
-        ops.fill_sparse_scaled_(result, g_sel_idx, g_sel_val, 1.0 / P)
+        if (self._sparse_ok and not exact and P > 1
+                and not ok.balanced_allgather):
+            # sparse hand-over: all_idx is ascending and unique by
+            # construction — the allgather concatenates rank-ordered
+            # segments, rank r's segment is the ascending compaction of its
+            # own region [bounds[r], bounds[r+1]), and the regions are
+            # disjoint and ordered by rank.  No filter (tau < 0).
+            self.sparse_result = SparseGrad(
+                g_sel_idx.to(torch.int32), g_sel_val, 1.0 / P, -1.0)
+        else:
+            ops.fill_sparse_scaled_(result, g_sel_idx, g_sel_val, 1.0 / P)
 
         self._residual_credit(st, idx, g_sel_idx, n, t.device)
         self._time(name, "merge", time.perf_counter() - s4)

@@ -175,9 +175,66 @@ def fused_adam_mirror_(param, grad, exp_avg, exp_avg_sq, param_bf16, lr, beta1,
 def scatter_gt_credit_(result, residual, idx, val, tau, scale=1.0) -> int:
     """Fused world-1 round-2 tail: where |val|>tau, result[idx]=val*scale
     and residual[idx]=0; returns the selected count.  `result` must be
-    zeroed by the caller."""
+    zeroed by the caller; `result=None` does the credit and the count only
+    (the sparse optimizer tail below needs no dense gradient)."""
+    if result is None:
+        return int(_backend(residual).credit_gt_(residual, idx, val, float(tau)))
     return int(_backend(result).scatter_gt_credit_(
         result, residual, idx, val, float(tau), float(scale)))
+
+
+# -- sparse optimizer tail ---------------------------------------------------
+# A sparse gradient (idx int32 ascending+unique, val fp32, scale, tau) stands
+# for the dense vector that is val[i]*scale at idx[i] where |val[i]| > tau
+# (tau < 0 keeps every entry) and +0.0 elsewhere: what fill_sparse_scaled_,
+# or zero + scatter_gt_credit_, would have written.
+
+def sparse_sumsq_into_(acc: torch.Tensor, idx, val, scale: float,
+                       tau: float) -> None:
+    """acc (fp64[1], same device) += sum of squares of the dense gradient a
+    sparse one stands for; no host sync on GPU."""
+    return _backend(val).sparse_sumsq_into_(acc, idx, val, float(scale),
+                                            float(tau))
+
+
+def grad_clip_scale_sparse(idx, val, scale: float, tau: float,
+                           max_norm: float, n: int) -> torch.Tensor:
+    """grad_clip_scale of the length-n dense gradient, from its sparse form;
+    no host sync.  The HIP op sums the kept entries in fp64 (n unused); the
+    CPU reference densifies to sum in the dense route's order."""
+    b = _backend(val)
+    if b is _ref:
+        return b.grad_clip_scale_sparse(idx, val, float(scale), float(tau),
+                                        float(max_norm), int(n))
+    return b.grad_clip_scale_sparse(idx, val, float(scale), float(tau),
+                                    float(max_norm))
+
+
+def fused_adam_sparse_(param, idx, val, base, scale, tau, exp_avg, exp_avg_sq,
+                       lr, beta1, beta2, eps, weight_decay, gscale=None):
+    """fused_adam_ on the slice [base, base+len(param)) of a sparse gradient:
+    bit-identical to densifying first, without the dense read."""
+    return _backend(param).fused_adam_sparse_(
+        param, idx, val, int(base), float(scale), float(tau), exp_avg,
+        exp_avg_sq, float(lr), float(beta1), float(beta2), float(eps),
+        float(weight_decay), gscale)
+
+
+def fused_adam_sparse_mirror_(param, idx, val, base, scale, tau, exp_avg,
+                              exp_avg_sq, param_bf16, lr, beta1, beta2, eps,
+                              weight_decay, gscale=None):
+    """fused_adam_sparse_ + bf16 weight-mirror write in one pass (GPU); the
+    CPU reference steps then casts."""
+    b = _backend(param)
+    if hasattr(b, "fused_adam_sparse_mirror_"):
+        return b.fused_adam_sparse_mirror_(
+            param, idx, val, int(base), float(scale), float(tau), exp_avg,
+            exp_avg_sq, param_bf16, float(lr), float(beta1), float(beta2),
+            float(eps), float(weight_decay), gscale)
+    b.fused_adam_sparse_(param, idx, val, int(base), float(scale), float(tau),
+                         exp_avg, exp_avg_sq, float(lr), float(beta1),
+                         float(beta2), float(eps), float(weight_decay), gscale)
+    param_bf16.copy_(param)
 
 
 # -- sparse wire codec ([idx int32 | val bits] per segment, fp32 or bf16) ---

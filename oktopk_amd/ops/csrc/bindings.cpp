@@ -43,6 +43,12 @@ void launch_clip_scale(const double*, float, float*, hipStream_t);
 void launch_adam(float*, const float*, float*, float*, void*, const float*, int64_t, float, float,
                  float, float, float, hipStream_t);
 void launch_sumsq(const float*, int64_t, double*, hipStream_t);
+void launch_sparse_sumsq(const float*, int64_t, float, float, double*, hipStream_t);
+int64_t adam_sparse_ntiles(int64_t);
+void launch_adam_sparse(float*, float*, float*, void*, const float*, int64_t,
+                        const int32_t*, const float*, int64_t, int32_t*, int64_t,
+                        float, float, float, float, float, float, float,
+                        hipStream_t);
 void launch_colsum_into_bf16(const void*, int64_t, int64_t, void*, int,
                              hipStream_t);
 bool ln_bwd_supported(int64_t H);
@@ -542,6 +548,105 @@ static torch::Tensor grad_clip_scale(torch::Tensor t, double max_norm) {
     launch_clip_scale(ss.data_ptr<double>(), (float)max_norm,
                       out.data_ptr<float>(), cur_stream());
     return out;
+}
+
+// -- sparse optimizer tail (kernels.hip, "sparse optimizer tail") -----------
+
+static void check_sparse_grad(const torch::Tensor& idx, const torch::Tensor& val) {
+    check_i32_1d(idx, "idx");
+    check_f32_1d(val, "val");
+    TORCH_CHECK(idx.numel() == val.numel(), "idx / val length mismatch");
+    TORCH_CHECK(idx.numel() < (int64_t)INT32_MAX, "selection too large");
+}
+
+static int64_t credit_gt_(torch::Tensor residual, torch::Tensor idx,
+                          torch::Tensor val, double tau) {
+    // scatter_gt_credit_ without the dense result: residual credit + count
+    check_f32_1d(residual, "residual");
+    check_sparse_grad(idx, val);
+    const at::cuda::CUDAGuard guard(residual.device());
+    auto cnt = torch::zeros({1}, residual.options().dtype(torch::kInt64));
+    launch_scatter_gt_credit(idx.data_ptr<int32_t>(), val.data_ptr<float>(),
+                             idx.numel(), (float)tau, 1.f, nullptr,
+                             residual.data_ptr<float>(),
+                             (unsigned long long*)cnt.data_ptr<int64_t>(),
+                             cur_stream());
+    return cnt.cpu().item<int64_t>();
+}
+
+static void sparse_sumsq_into_(torch::Tensor acc, torch::Tensor idx,
+                               torch::Tensor val, double scale, double tau) {
+    // sumsq_into_ of the dense gradient a sparse one stands for
+    check_sparse_grad(idx, val);
+    TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == torch::kFloat64 &&
+                acc.numel() == 1 && acc.device() == val.device(),
+                "acc must be a 1-elem fp64 tensor on val's device");
+    const at::cuda::CUDAGuard guard(val.device());
+    launch_sparse_sumsq(val.data_ptr<float>(), val.numel(), (float)scale,
+                        (float)tau, acc.data_ptr<double>(), cur_stream());
+}
+
+static torch::Tensor grad_clip_scale_sparse(torch::Tensor idx, torch::Tensor val,
+                                            double scale, double tau,
+                                            double max_norm) {
+    // grad_clip_scale of the dense gradient a sparse one stands for: fp64
+    // sum over the kept entries, then the same clip_scale kernel; no sync
+    check_sparse_grad(idx, val);
+    const at::cuda::CUDAGuard guard(val.device());
+    auto ss = torch::zeros({1}, val.options().dtype(torch::kFloat64));
+    launch_sparse_sumsq(val.data_ptr<float>(), val.numel(), (float)scale,
+                        (float)tau, ss.data_ptr<double>(), cur_stream());
+    auto out = torch::empty({1}, val.options());
+    launch_clip_scale(ss.data_ptr<double>(), (float)max_norm,
+                      out.data_ptr<float>(), cur_stream());
+    return out;
+}
+
+static void adam_sparse_impl(torch::Tensor& p, torch::Tensor& idx,
+                             torch::Tensor& val, int64_t base, double scale,
+                             double tau, torch::Tensor& m, torch::Tensor& v,
+                             void* p_bf16, double lr, double b1, double b2,
+                             double eps, double wd,
+                             const c10::optional<torch::Tensor>& gscale) {
+    check_f32_1d(p, "p");
+    check_f32_1d(m, "m");
+    check_f32_1d(v, "v");
+    check_sparse_grad(idx, val);
+    TORCH_CHECK(m.numel() == p.numel() && v.numel() == p.numel(),
+                "p / m / v length mismatch");
+    TORCH_CHECK(base >= 0, "base must be >= 0");
+    const at::cuda::CUDAGuard guard(p.device());
+    auto tile_start = torch::empty({adam_sparse_ntiles(p.numel()) + 1},
+                                   idx.options());
+    launch_adam_sparse(p.data_ptr<float>(), m.data_ptr<float>(),
+                       v.data_ptr<float>(), p_bf16, gscale_ptr(gscale),
+                       p.numel(), idx.data_ptr<int32_t>(), val.data_ptr<float>(),
+                       idx.numel(), tile_start.data_ptr<int32_t>(), base,
+                       (float)scale, (float)tau, (float)lr, (float)b1,
+                       (float)b2, (float)eps, (float)wd, cur_stream());
+}
+
+static void fused_adam_sparse_(torch::Tensor p, torch::Tensor idx,
+                               torch::Tensor val, int64_t base, double scale,
+                               double tau, torch::Tensor m, torch::Tensor v,
+                               double lr, double b1, double b2, double eps,
+                               double wd, c10::optional<torch::Tensor> gscale) {
+    adam_sparse_impl(p, idx, val, base, scale, tau, m, v, nullptr, lr, b1, b2,
+                     eps, wd, gscale);
+}
+
+static void fused_adam_sparse_mirror_(torch::Tensor p, torch::Tensor idx,
+                                      torch::Tensor val, int64_t base,
+                                      double scale, double tau, torch::Tensor m,
+                                      torch::Tensor v, torch::Tensor p_bf16,
+                                      double lr, double b1, double b2,
+                                      double eps, double wd,
+                                      c10::optional<torch::Tensor> gscale) {
+    TORCH_CHECK(p_bf16.is_cuda() && p_bf16.scalar_type() == torch::kBFloat16 &&
+                p_bf16.is_contiguous() && p_bf16.numel() == p.numel(),
+                "p_bf16: contiguous cuda bf16 of p's length");
+    adam_sparse_impl(p, idx, val, base, scale, tau, m, v, p_bf16.data_ptr(), lr,
+                     b1, b2, eps, wd, gscale);
 }
 
 static void colsum_bf16_into(torch::Tensor gy, torch::Tensor dst,
@@ -1114,6 +1219,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "residual[idx]=0 where |val|>tau; returns the count");
     m.def("grad_clip_scale", &grad_clip_scale,
           "device-resident clip factor min(1, max/||t||) (no host sync)");
+    m.def("credit_gt_", &credit_gt_,
+          "residual[idx]=0 where |val|>tau; returns the count (no dense result)");
+    m.def("sparse_sumsq_into_", &sparse_sumsq_into_,
+          "acc (fp64[1]) += sum((val*scale)^2) over entries with |val|>tau");
+    m.def("grad_clip_scale_sparse", &grad_clip_scale_sparse,
+          "grad_clip_scale of a sparse gradient (idx, val, scale, tau)");
+    m.def("fused_adam_sparse_", &fused_adam_sparse_,
+          "fused Adam step, gradient given as (idx, val, base, scale, tau)",
+          py::arg("p"), py::arg("idx"), py::arg("val"), py::arg("base"),
+          py::arg("scale"), py::arg("tau"), py::arg("m"), py::arg("v"),
+          py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
+          py::arg("wd"), py::arg("gscale") = py::none());
+    m.def("fused_adam_sparse_mirror_", &fused_adam_sparse_mirror_,
+          "fused_adam_sparse_ + bf16 weight-mirror write",
+          py::arg("p"), py::arg("idx"), py::arg("val"), py::arg("base"),
+          py::arg("scale"), py::arg("tau"), py::arg("m"), py::arg("v"),
+          py::arg("p_bf16"), py::arg("lr"), py::arg("b1"), py::arg("b2"),
+          py::arg("eps"), py::arg("wd"), py::arg("gscale") = py::none());
     m.def("l2norm", &l2norm, "L2 norm (fp64 accumulate)");
     m.def("colsum_bf16_into", &colsum_bf16_into,
           "bias grad: dst (=|+=) column sum of bf16 [R, C], one launch",

@@ -416,7 +416,9 @@ extern "C" void launch_zero_at(float* dest, const int32_t* idx, int64_t m,
 // the local one), and count it.  Replaces the reference-shaped chain
 // boolean-mask -> nonzero (host sync) -> two gathers -> fill_sparse ->
 // masked credit (VGG/allreducer.py:853-1081's owner filter, degenerate
-// P==1 case) with one pass over the ~k selection.
+// P==1 case) with one pass over the ~k selection.  A null `result` does the
+// credit and the count only: the sparse optimizer tail below consumes
+// (idx, val, tau) directly and needs no dense gradient.
 __global__ void scatter_gt_credit_kernel(const int32_t* __restrict__ idx,
                                          const float* __restrict__ val,
                                          int64_t m, uint32_t tau_bits,
@@ -431,7 +433,7 @@ __global__ void scatter_gt_credit_kernel(const int32_t* __restrict__ idx,
         float v = val[i];
         if (sel_gt(abs_bits(v), tau_bits)) {
             int32_t j = idx[i];
-            result[j] = v * scale;
+            if (result) result[j] = v * scale;
             residual[j] = 0.f;
             ++c;
         }
@@ -890,6 +892,216 @@ extern "C" void launch_sumsq(const float* t, int64_t n, double* out, hipStream_t
     int64_t n4 = ((uintptr_t)t & 15) == 0 ? n >> 2 : 0;
     hipLaunchKernelGGL(sumsq_kernel, dim3(n_blocks(n, 8)), dim3(BLOCK), 0, stream,
                        t, n, n4, out);
+}
+
+// ---------------------------------------------------------------------------
+// sparse optimizer tail: clip scale and Adam straight from the selection
+//
+// A sparse gradient is (idx int32 ascending+unique, val, m, scale, tau):
+// dense element j is val[i]*scale where idx[i] == j and |val[i]| > tau
+// (tau < 0 keeps everything), +0.0f elsewhere — what fill_sparse_scaled_ or
+// zero + scatter_gt_credit_ would have written.  Consuming it directly
+// drops the zero fill, the scatter, the dense sum of squares and Adam's
+// gradient read: three tensor-scale passes that only carried ~k numbers.
+// ---------------------------------------------------------------------------
+#define ADAM_TILE (BLOCK * 4)  // elements per block per float4 iteration
+
+// fp64 sum of (val*scale)^2 over the kept entries; the product is rounded
+// to fp32 first, as the scatter stores it, so each term equals the dense
+// route's term and only the (already atomic-ordered) summation differs
+__global__ void sparse_sumsq_kernel(const float* __restrict__ val, int64_t m,
+                                    float scale, uint32_t tau_bits,
+                                    double* __restrict__ out) {
+    int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * BLOCK;
+    double acc = 0.0;
+    for (; i < m; i += stride) {
+        float x = val[i];
+        if (sel_gt(abs_bits(x), tau_bits)) {
+            float g = x * scale;
+            acc += (double)g * g;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        acc += __shfl_down(acc, off, 64);
+    __shared__ double ws[WAVES_PER_BLOCK];
+    int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) ws[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0;
+        for (int w = 0; w < WAVES_PER_BLOCK; ++w) s += ws[w];
+        atomicAdd(out, s);
+    }
+}
+
+extern "C" void launch_sparse_sumsq(const float* val, int64_t m, float scale,
+                                    float tau, double* out, hipStream_t stream) {
+    if (m <= 0) return;
+    hipLaunchKernelGGL(sparse_sumsq_kernel, dim3(n_blocks(m, 4)), dim3(BLOCK), 0,
+                       stream, val, m, scale, tau_to_bits(tau), out);
+}
+
+// tile_start[t] = first entry with idx >= base + min(t*ADAM_TILE, n), for
+// t in [0, ntiles]: tile t of the slice [base, base+n) owns the entries
+// [tile_start[t], tile_start[t+1]); entries below or above the slice fall
+// outside every tile.  One binary search per tile over an L2-resident list.
+__global__ void sparse_tile_start_kernel(const int32_t* __restrict__ idx,
+                                         int64_t m, int64_t base, int64_t n,
+                                         int64_t ntiles,
+                                         int32_t* __restrict__ tile_start) {
+    int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * BLOCK;
+    for (; t <= ntiles; t += stride) {
+        int64_t off = t * ADAM_TILE;
+        if (off > n) off = n;
+        int64_t target = base + off;
+        int64_t lo = 0, hi = m;
+        while (lo < hi) {
+            int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)idx[mid] < target) lo = mid + 1; else hi = mid;
+        }
+        tile_start[t] = (int32_t)lo;
+    }
+}
+
+// adam_one with its multiply-adds written out and contraction off.  hipcc
+// contracts adam_one's `a*b + c*d` sums one way in adam_kernel's float4
+// loop (packed math: the gradient product is the fused one) and the other
+// way in its scalar loop (the state product is); inside a different loop
+// body it need not choose the same, and the two roundings differ in the
+// last bit.  These are the forms adam_kernel compiles to — VEC for the
+// float4 loop — so the sparse kernel reproduces it bit for bit;
+// tests/test_sparse_step_gpu.py compares the two kernels on both paths.
+template <bool VEC>
+__device__ __forceinline__ float adam_one_as_compiled(float pi, float gi,
+                                                      float& mi, float& vi,
+                                                      float lr, float b1,
+                                                      float b2, float eps,
+                                                      float wd) {
+#pragma clang fp contract(off)
+    const float c1 = 1.f - b1, c2 = 1.f - b2;
+    if (VEC) {
+        mi = __builtin_fmaf(c1, gi, mi * b1);
+        vi = __builtin_fmaf(c2 * gi, gi, vi * b2);
+    } else {
+        mi = __builtin_fmaf(mi, b1, c1 * gi);
+        vi = __builtin_fmaf(vi, b2, (c2 * gi) * gi);
+    }
+    const float up = __builtin_fmaf(wd, pi, mi / (sqrtf(vi) + eps));
+    return __builtin_fmaf(-lr, up, pi);
+}
+
+// adam_kernel with the gradient taken from the sparse form: same update,
+// same gi*gs, same float4 / scalar-tail split and the same tile-to-block
+// mapping (tile T = the 256 float4 a block covers in one grid-stride
+// iteration).  A block reads its tile's [start, end) — block-uniform, so
+// the hit loop's idx/val loads are broadcasts — and each lane patches the
+// component it owns.  An element without a kept hit feeds +0.0f through the
+// unchanged formula, so every bit (the sign of a -0 exp_avg included)
+// matches the dense route.
+__global__ void adam_sparse_kernel(float* __restrict__ p, float* __restrict__ m,
+                                   float* __restrict__ v,
+                                   short* __restrict__ p_bf16,
+                                   const float* __restrict__ gscale_ptr,
+                                   int64_t n, int64_t n4,
+                                   const int32_t* __restrict__ idx,
+                                   const float* __restrict__ val,
+                                   const int32_t* __restrict__ tile_start,
+                                   int64_t base, float scale, uint32_t tau_bits,
+                                   float lr, float b1, float b2, float eps,
+                                   float wd) {
+    const float gs = gscale_ptr ? *gscale_ptr : 1.f;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    short4* b4 = reinterpret_cast<short4*>(p_bf16);
+    const int64_t nt4 = (n4 + BLOCK - 1) / BLOCK;
+    int64_t T = blockIdx.x;
+    int hs = 0, he = 0;
+    if (T < nt4) { hs = tile_start[T]; he = tile_start[T + 1]; }
+    for (; T < nt4; T += gridDim.x) {
+        // the next tile's range is fetched one iteration ahead, so the hit
+        // loop's loads are the only dependent latency inside an iteration
+        const int64_t Tn = T + gridDim.x;
+        int hs_n = 0, he_n = 0;
+        if (Tn < nt4) { hs_n = tile_start[Tn]; he_n = tile_start[Tn + 1]; }
+        const int64_t i = T * BLOCK + threadIdx.x;
+        if (i < n4) {
+            float4 pi = p4[i], mi = m4[i], vi = v4[i];
+            float4 gi = make_float4(0.f, 0.f, 0.f, 0.f);
+            const int64_t e0 = base + 4 * i;
+            for (int h = hs; h < he; ++h) {
+                const float x = val[h];
+                const int64_t j = (int64_t)idx[h] - e0;
+                const bool keep = sel_gt(abs_bits(x), tau_bits);
+                const float g = x * scale;
+                gi.x = (keep & (j == 0)) ? g : gi.x;
+                gi.y = (keep & (j == 1)) ? g : gi.y;
+                gi.z = (keep & (j == 2)) ? g : gi.z;
+                gi.w = (keep & (j == 3)) ? g : gi.w;
+            }
+            pi.x = adam_one_as_compiled<true>(pi.x, gi.x * gs, mi.x, vi.x,
+                                             lr, b1, b2, eps, wd);
+            pi.y = adam_one_as_compiled<true>(pi.y, gi.y * gs, mi.y, vi.y,
+                                             lr, b1, b2, eps, wd);
+            pi.z = adam_one_as_compiled<true>(pi.z, gi.z * gs, mi.z, vi.z,
+                                             lr, b1, b2, eps, wd);
+            pi.w = adam_one_as_compiled<true>(pi.w, gi.w * gs, mi.w, vi.w,
+                                             lr, b1, b2, eps, wd);
+            m4[i] = mi; v4[i] = vi; p4[i] = pi;
+            if (p_bf16)
+                b4[i] = make_short4(adam_f2b(pi.x), adam_f2b(pi.y),
+                                    adam_f2b(pi.z), adam_f2b(pi.w));
+        }
+        hs = hs_n; he = he_n;
+    }
+    // scalar tail (n % 4) and the unaligned-base fallback (n4 == 0): each
+    // element looks its own tile up — never the hot path
+    const int64_t stride = (int64_t)gridDim.x * BLOCK;
+    for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
+         i += stride) {
+        const int64_t T = i / ADAM_TILE;
+        const int hs = tile_start[T], he = tile_start[T + 1];
+        const int64_t e0 = base + i;
+        float gi = 0.f;
+        for (int h = hs; h < he; ++h) {
+            const float x = val[h];
+            if ((int64_t)idx[h] == e0 && sel_gt(abs_bits(x), tau_bits))
+                gi = x * scale;
+        }
+        float mi = m[i], vi = v[i];
+        float pn = adam_one_as_compiled<false>(p[i], gi * gs, mi, vi, lr, b1, b2,
+                                                eps, wd);
+        m[i] = mi; v[i] = vi; p[i] = pn;
+        if (p_bf16) p_bf16[i] = adam_f2b(pn);
+    }
+}
+
+extern "C" int64_t adam_sparse_ntiles(int64_t n) {
+    return (n + ADAM_TILE - 1) / ADAM_TILE;
+}
+
+// tile_start: int32 workspace of adam_sparse_ntiles(n) + 1 entries
+extern "C" void launch_adam_sparse(float* p, float* m, float* v, void* p_bf16,
+                                   const float* gscale, int64_t n,
+                                   const int32_t* idx, const float* val,
+                                   int64_t m_entries, int32_t* tile_start,
+                                   int64_t base, float scale, float tau,
+                                   float lr, float b1, float b2, float eps,
+                                   float wd, hipStream_t stream) {
+    if (n <= 0) return;
+    int64_t ntiles = adam_sparse_ntiles(n);
+    hipLaunchKernelGGL(sparse_tile_start_kernel, dim3(n_blocks(ntiles + 1)),
+                       dim3(BLOCK), 0, stream, idx, m_entries, base, n, ntiles,
+                       tile_start);
+    bool aligned = (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
+                   (((uintptr_t)p_bf16) & 7) == 0;
+    int64_t n4 = aligned ? n >> 2 : 0;
+    hipLaunchKernelGGL(adam_sparse_kernel, dim3(n_blocks(n, 8)), dim3(BLOCK), 0,
+                       stream, p, m, v, (short*)p_bf16, gscale, n, n4, idx, val,
+                       tile_start, base, scale, tau_to_bits(tau), lr, b1, b2,
+                       eps, wd);
 }
 
 __device__ __forceinline__ float ks_b2f(short u) {

@@ -287,6 +287,61 @@ def scatter_gt_credit_(result, residual, idx, val, tau, scale=1.0) -> int:
     return int(sel.sum())
 
 
+def credit_gt_(residual, idx, val, tau) -> int:
+    """scatter_gt_credit_ without the dense result: residual[idx] = 0 where
+    |val| > tau; returns the count."""
+    sel = val.abs() > tau
+    residual[idx.long()[sel]] = 0.0
+    return int(sel.sum())
+
+
+# -- sparse optimizer tail --------------------------------------------------
+# A sparse gradient (idx int32 ascending+unique, val fp32, scale, tau) stands
+# for the dense vector that is val[i]*scale at idx[i] where |val[i]| > tau
+# (tau < 0 keeps every entry) and +0.0 elsewhere.
+
+def _sparse_kept(val: torch.Tensor, tau: float) -> torch.Tensor:
+    if tau < 0:
+        return torch.ones_like(val, dtype=torch.bool)
+    return val.abs() > tau
+
+
+def densify_sparse_grad(idx, val, base: int, n: int, scale: float, tau: float):
+    """The slice [base, base+n) of the dense gradient a sparse one stands
+    for, as a fresh fp32 tensor."""
+    g = torch.zeros(n, dtype=torch.float32, device=val.device)
+    j = idx.long() - int(base)
+    keep = _sparse_kept(val, tau) & (j >= 0) & (j < n)
+    g[j[keep]] = val[keep] * scale
+    return g
+
+
+def sparse_sumsq_into_(acc: torch.Tensor, idx, val, scale: float,
+                       tau: float) -> None:
+    """acc (fp64[1]) += sum of squares of the dense gradient: the kept
+    val*scale products, rounded to fp32 as the scatter stores them."""
+    g = val[_sparse_kept(val, tau)] * scale
+    acc += (g.double() ** 2).sum()
+
+
+def grad_clip_scale_sparse(idx, val, scale: float, tau: float,
+                           max_norm: float, n: int) -> torch.Tensor:
+    """grad_clip_scale of the length-n dense gradient.  Densifies, so the
+    norm is summed in exactly the dense route's order and the two routes
+    agree to the bit (the HIP op sums the kept entries only and ignores n)."""
+    return grad_clip_scale(densify_sparse_grad(idx, val, 0, n, scale, tau),
+                           max_norm)
+
+
+def fused_adam_sparse_(param, idx, val, base, scale, tau, exp_avg, exp_avg_sq,
+                       lr, beta1, beta2, eps, weight_decay, gscale=None) -> None:
+    """fused_adam_ with the gradient slice [base, base+len(param)) given in
+    sparse form: densify into a temporary, then the dense update."""
+    g = densify_sparse_grad(idx, val, base, param.numel(), scale, tau)
+    fused_adam_(param, g, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
+                weight_decay, gscale)
+
+
 # -- sparse wire codec ------------------------------------------------------
 # Wire layout (AllReducer._pack / _unpack / _pack_ints): segment j with c_j
 # elements is c_j int32 indices followed by the values — c_j fp32 words, or

@@ -19,6 +19,7 @@ Two surfaces, mirroring the reference:
 from __future__ import annotations
 
 import math
+import os
 import queue
 import threading
 from typing import Dict, Iterable, List, Optional, Tuple
@@ -620,7 +621,13 @@ class FlatBertAdam:
 
     def step(self):
         self._settle_direct_grad()
-        # 1. sparse allreduce of the whole flat gradient
+        # 1. sparse allreduce of the whole flat gradient.  The engine may
+        # hand the result over in sparse form (AllReducer.run sparse_ok):
+        # flat_grad is then left unwritten and clip + Adam below consume the
+        # ~k selected entries directly — same bits, three tensor-scale
+        # passes less.  OKTOPK_SPARSE_STEP=0 keeps the dense hand-over.
+        sparse_ok = os.environ.get("OKTOPK_SPARSE_STEP", "1") != "0"
+        self.reducer.sparse_result = None
         if self.cfg.compressor in ("dense", "none") and self.model_dtype != torch.float32:
             # dense baseline: allreduce the bf16 grads directly (half wire
             # volume — the right dense baseline on MI355X), then upcast
@@ -628,16 +635,23 @@ class FlatBertAdam:
             self.flat_grad.copy_(self.flat_grad_model)
         elif self.flat_grad_model is not self.flat_grad:
             # bf16 grads: the upcast is fused into the engine's EF restore
-            self.reducer.run("flat", self.flat_grad, grad_src=self.flat_grad_model)
+            self.reducer.run("flat", self.flat_grad, grad_src=self.flat_grad_model,
+                             sparse_ok=sparse_ok)
         else:
-            self.reducer.run("flat", self.flat_grad)
+            self.reducer.run("flat", self.flat_grad, sparse_ok=sparse_ok)
+        sg = self.reducer.sparse_result
         # 2. grad clip on the reduced gradient (reference optimization.py:197)
         # — device-resident: the clip factor stays on GPU and is applied by
         # the Adam kernel's gradient read (no host sync, no extra full-
         # tensor mul pass)
         gscale = None
         if self.max_grad_norm and self.max_grad_norm > 0:
-            gscale = ops.grad_clip_scale(self.flat_grad, self.max_grad_norm)
+            if sg is not None:
+                gscale = ops.grad_clip_scale_sparse(
+                    sg.idx, sg.val, sg.scale, sg.tau, self.max_grad_norm,
+                    self.numel)
+            else:
+                gscale = ops.grad_clip_scale(self.flat_grad, self.max_grad_norm)
         # 3. fused Adam: one launch per weight-decay group (2 total); on
         # the bf16 path the model-weight mirror is written BY the Adam
         # kernel (saves a separate 660 MB cast pass)
@@ -646,7 +660,24 @@ class FlatBertAdam:
         d = self.decay_numel
         mirrored = self.flat_param_model is not self.flat_param
         def _adam(sl, wd):
-            if mirrored:
+            if sg is not None:
+                # `base`: the slice's offset in the flat layout; entries of
+                # the selection outside the slice are ignored by the op
+                base = sl.start or 0
+                if mirrored:
+                    ops.fused_adam_sparse_mirror_(
+                        self.flat_param[sl], sg.idx, sg.val, base, sg.scale,
+                        sg.tau, self.exp_avg[sl], self.exp_avg_sq[sl],
+                        self.flat_param_model[sl], lr, b1, b2, self.eps, wd,
+                        gscale=gscale,
+                    )
+                else:
+                    ops.fused_adam_sparse_(
+                        self.flat_param[sl], sg.idx, sg.val, base, sg.scale,
+                        sg.tau, self.exp_avg[sl], self.exp_avg_sq[sl], lr, b1,
+                        b2, self.eps, wd, gscale=gscale,
+                    )
+            elif mirrored:
                 ops.fused_adam_mirror_(
                     self.flat_param[sl], self.flat_grad[sl], self.exp_avg[sl],
                     self.exp_avg_sq[sl], self.flat_param_model[sl], lr, b1, b2,

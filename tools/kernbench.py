@@ -236,6 +236,60 @@ def gauss_rows(reps, sizes=(109_500_000, 25_000_000), density=0.001,
                       f"{ts[len(ts) // 2]:10.3f} {ts[0]:9.3f} {ts[-1]:9.3f}")
 
 
+def sparse_step_rows(iters, density=0.001):
+    """The optimizer tail at the 109.5 M flat scale with k = 0.1 %: the dense
+    hand-over (zero fill + scatter + dense sum of squares + Adam over p, g,
+    m, v and the bf16 mirror) against the sparse pair (grad_clip_scale_sparse
+    + fused_adam_sparse_mirror_).  Bytes are the algorithm's, from the
+    shapes: Adam reads p, m, v (+g dense) and writes p, m, v and the bf16
+    mirror — 30 B/element dense, 26 B/element sparse.  The count readback of
+    scatter_gt_credit_ is left out of both arms (credit only through
+    zero_at_), so the rows time device work, not the host sync."""
+    g = torch.Generator().manual_seed(0)
+    k = int(N * density)
+    idx = torch.randperm(N, generator=g)[:k].sort().values.to(torch.int32).cuda()
+    val = torch.randn(k, generator=g).cuda()
+    p = torch.randn(N, generator=g).cuda()
+    m = torch.zeros(N, device="cuda")
+    v = torch.zeros(N, device="cuda")
+    mirror = torch.zeros(N, dtype=torch.bfloat16, device="cuda")
+    dense = torch.empty(N, device="cuda")
+    adam = (1e-3, 0.9, 0.999, 1e-6, 0.01)
+    print(f"# N={N}  entries={k}")
+
+    def dense_tail():
+        H.fill_sparse_scaled_(dense, idx, val, 1.0)
+        gs = H.grad_clip_scale(dense, 1.0)
+        H.fused_adam_mirror_(p, dense, m, v, mirror, *adam, gs)
+
+    def sparse_tail():
+        gs = H.grad_clip_scale_sparse(idx, val, 1.0, -1.0, 1.0)
+        H.fused_adam_sparse_mirror_(p, idx, val, 0, 1.0, -1.0, m, v, mirror,
+                                    *adam, gs)
+
+    gs1 = H.grad_clip_scale_sparse(idx, val, 1.0, -1.0, 1.0)
+    rows = []
+    for name, fn, nbytes in (
+        ("fill_sparse_scaled (zero+scatter)",
+         lambda: H.fill_sparse_scaled_(dense, idx, val, 1.0), 4 * N + 12 * k),
+        ("grad_clip_scale (dense)",
+         lambda: H.grad_clip_scale(dense, 1.0), 4 * N),
+        ("adam mirror (dense g)",
+         lambda: H.fused_adam_mirror_(p, dense, m, v, mirror, *adam, gs1), 30 * N),
+        ("dense tail (all three)", dense_tail, (4 + 4 + 30) * N + 12 * k),
+        ("grad_clip_scale_sparse",
+         lambda: H.grad_clip_scale_sparse(idx, val, 1.0, -1.0, 1.0), 4 * k),
+        ("adam mirror (sparse g)",
+         lambda: H.fused_adam_sparse_mirror_(p, idx, val, 0, 1.0, -1.0, m, v,
+                                             mirror, *adam, gs1),
+         26 * N + 8 * k),
+        ("sparse tail (both)", sparse_tail, 26 * N + 12 * k),
+    ):
+        dev_us, _wall = time_both(fn, iters)
+        rows.append((name, dev_us / 1000, nbytes / GB / (dev_us / 1e6)))
+    return rows
+
+
 def print_rows(rows):
     print(f"{'op':28s} {'ms':>9s} {'GB/s':>8s}")
     for name, ms, bw in rows:
@@ -248,10 +302,14 @@ def main():
                     help="calls per timed window (default 20; 1000 for the "
                          "microsecond-scale --only wire rows; repeats per "
                          "row, default 15, for --only gauss)")
-    ap.add_argument("--only", default="", choices=["", "colsum", "wire", "gauss"],
+    ap.add_argument("--only", default="",
+                    choices=["", "colsum", "wire", "gauss", "sparse_step"],
                     help="run just one group of rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.only == "sparse_step":
+        print_rows(sparse_step_rows(args.iters or 20))
+        return
     if args.only == "colsum":
         print_rows(colsum_rows())
         return
