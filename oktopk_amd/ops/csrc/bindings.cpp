@@ -10,6 +10,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "colsum_exact_config.h"
+
 // launchers from kernels.hip
 extern "C" {
 void launch_count_gt(const float*, int64_t, float, unsigned long long*, hipStream_t);
@@ -50,6 +52,8 @@ void launch_adam_sparse(float*, float*, float*, void*, const float*, int64_t,
                         float, float, float, float, float, float, float,
                         hipStream_t);
 void launch_colsum_into_bf16(const void*, int64_t, int64_t, void*, int,
+                             hipStream_t);
+int launch_colsum_exact_bf16(const void*, int64_t, int64_t, void*, int, int,
                              hipStream_t);
 bool ln_bwd_supported(int64_t H);
 int ln_bwd_blocks(int64_t rows);
@@ -668,17 +672,68 @@ static void colsum_bf16_into(torch::Tensor gy, torch::Tensor dst,
                             accumulate ? 1 : 0, cur_stream());
 }
 
+static py::object colsum_exact_config(int64_t R, int64_t C, int64_t src_addr,
+                                      int64_t num_mp, int64_t max_threads_per_mp,
+                                      int64_t warp_size) {
+    // the port of torch's reduce configuration, for tests and tools:
+    // (V, bw, bh, split, ctas), or None where it is unsupported
+    auto cfg = colsum_exact::derive(R, C, (uint64_t)src_addr, (int)num_mp,
+                                    (int)max_threads_per_mp, (int)warp_size);
+    if (!cfg.supported) return py::none();
+    return py::make_tuple(cfg.V, cfg.bw, cfg.bh, cfg.split, cfg.ctas);
+}
+
+static bool colsum_bf16_into_exact(torch::Tensor gy, torch::Tensor dst,
+                                   bool accumulate) {
+    // dst[C] = column sum of a contiguous bf16 [R, C], summed in the order
+    // of at::sum_out(dst, gy, {0}) on this device, so it leaves the same
+    // bits.  One launch.  False: this shape / address / device is outside
+    // the ported family, and nothing was written.
+    //
+    // accumulate is always unsupported.  The form to match would be
+    // dst.add_(at::sum(gy, {0}, false, kFloat)); the fp32 sum has the same
+    // order, but torch's bf16 += fp32 add is not one function of its
+    // operands: measured on MI355X (torch 2.10), [768 .. 15000] elements give
+    // bf16(float(dst) + s), while [30520] and [30522] give
+    // bf16(float(dst) + float(bf16(s))), 124 of 30522 elements apart.  That
+    // switch lies in the elementwise kernels, not in the reduction, so the
+    // accumulating caller keeps torch's two calls.  The captured fwd+bwd
+    // only ever overwrites.
+    TORCH_CHECK(gy.is_cuda() && gy.scalar_type() == torch::kBFloat16 &&
+                gy.dim() == 2, "gy: cuda bf16 [R, C]");
+    TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == torch::kBFloat16 &&
+                dst.is_contiguous() && dst.device() == gy.device() &&
+                dst.numel() == gy.size(1),
+                "dst: contiguous cuda bf16 [C] on gy's device");
+    if (accumulate || !gy.is_contiguous()) return false;
+    const int64_t R = gy.size(0), C = gy.size(1);
+    const at::cuda::CUDAGuard guard(gy.device());
+    const auto* prop = at::cuda::getCurrentDeviceProperties();
+    auto cfg = colsum_exact::derive(R, C, (uint64_t)(uintptr_t)gy.data_ptr(),
+                                    prop->multiProcessorCount,
+                                    prop->maxThreadsPerMultiProcessor,
+                                    at::cuda::warp_size());
+    if (!cfg.supported) return false;
+    return launch_colsum_exact_bf16(gy.data_ptr(), R, C, dst.data_ptr(),
+                                    cfg.split ? cfg.bh : 1, cfg.ctas,
+                                    cur_stream()) != 0;
+}
+
 static torch::Tensor linear_bwd_into(torch::Tensor gy, torch::Tensor x,
                                      torch::Tensor w,
                                      c10::optional<torch::Tensor> gw_dst,
                                      c10::optional<torch::Tensor> gb_dst,
-                                     bool accumulate, bool bias_kernel) {
+                                     bool accumulate, bool bias_kernel,
+                                     bool bias_exact) {
     // backward of y = x W^T + b with the parameter gradients written
     // straight into their slots: gW is the GEMM's own output (beta = 0, or
     // beta = 1 when accumulating) and gb a column reduction whose output is
-    // the slot, so neither needs a temporary plus an add.  By default both
-    // leave exactly the bits autograd's zero + accumulate left; bias_kernel
-    // swaps torch's reduction for our one-launch column sum.  Returns gx.
+    // the slot, so neither needs a temporary plus an add.  Both leave
+    // exactly the bits autograd's zero + accumulate left: bias_exact runs
+    // the one-launch column sum that follows torch's summation order where
+    // it is supported and torch's reduction elsewhere.  bias_kernel (wins
+    // over bias_exact) selects the older one-launch column sum, whose order
+    // is its own.  Returns gx.
     TORCH_CHECK(gy.is_cuda() && gy.scalar_type() == torch::kBFloat16 &&
                 x.scalar_type() == torch::kBFloat16 &&
                 w.scalar_type() == torch::kBFloat16 && w.dim() == 2,
@@ -707,6 +762,8 @@ static torch::Tensor linear_bwd_into(torch::Tensor gy, torch::Tensor x,
             // one launch of ours; sums in another order than torch's
             // reduction, so a rare element rounds to the neighbouring bf16
             colsum_bf16_into(gy2, gb, accumulate);
+        } else if (bias_exact && colsum_bf16_into_exact(gy2, gb, accumulate)) {
+            // one launch of ours, torch's bits
         } else {
             // torch's own column reduction with the slot as its output:
             // the bits autograd's `0 + sum` left there, minus the add
@@ -1241,6 +1298,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("colsum_bf16_into", &colsum_bf16_into,
           "bias grad: dst (=|+=) column sum of bf16 [R, C], one launch",
           py::arg("gy"), py::arg("dst"), py::arg("accumulate") = false);
+    m.def("colsum_bf16_into_exact", &colsum_bf16_into_exact,
+          "bias grad in torch's summation order (bit-equal to sum_out); "
+          "False = unsupported (accumulate always is), nothing written",
+          py::arg("gy"), py::arg("dst"), py::arg("accumulate") = false);
+    m.def("colsum_exact_config", &colsum_exact_config,
+          "torch's reduce configuration (V, bw, bh, split, ctas) for a "
+          "dim-0 sum of a contiguous bf16 [R, C], or None",
+          py::arg("R"), py::arg("C"), py::arg("src_addr"), py::arg("num_mp"),
+          py::arg("max_threads_per_mp"), py::arg("warp_size"));
     m.def("ln_bwd_supported", &ln_bwd_into_supported,
           "hidden sizes ln_bwd_into handles");
     m.def("ln_bwd_into", &ln_bwd_into,
@@ -1252,7 +1318,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "Linear backward; gW/gb written into their gradient slots, returns gx",
           py::arg("gy"), py::arg("x"), py::arg("w"), py::arg("gw_dst"),
           py::arg("gb_dst"), py::arg("accumulate") = false,
-          py::arg("bias_kernel") = false);
+          py::arg("bias_kernel") = false, py::arg("bias_exact") = false);
     m.def("attn_rowdot", &attn_rowdot,
           "flash-bwd D: per-(head,row) dot of gO and O (head_dim 64)");
     m.def("sumsq_into_", &sumsq_into_,

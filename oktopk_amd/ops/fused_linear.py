@@ -77,9 +77,10 @@ def fused_linear_gelu(x: torch.Tensor, weight: torch.Tensor, bias=None) -> torch
 # temporary gradient plus an accumulate kernel `slot += g` onto a slot that
 # zero_grad() just zeroed.  Here the weight-gradient GEMM has the slot as its
 # output and the bias gradient is a column reduction whose output is the slot
-# (torch's own, bit-identical to before; or with OKTOPK_COLSUM_BIAS=1 the
-# one-launch column-sum kernel), and the node hands autograd an undefined
-# gradient for both, so its accumulate step has nothing to do.
+# (the one-launch kernel that sums in torch's order, bit-identical to torch's
+# own reduction; see bias_grad_mode for the switch), and the node hands
+# autograd an undefined gradient for both, so its accumulate step has nothing
+# to do.
 #
 # Protocol (three attributes on the Parameter, nothing else is shared):
 #   * the MODEL calls mark_every_backward(p) on parameters whose Linear runs
@@ -98,6 +99,25 @@ def fused_linear_gelu(x: torch.Tensor, weight: torch.Tensor, bias=None) -> torch
 
 _SLOT_ATTR = "_oktopk_grad_slot"
 _EVERY_BWD_ATTR = "_oktopk_every_backward"
+
+
+def bias_grad_mode() -> str:
+    """Which column reduction writes a bound bias-gradient slot.
+
+    OKTOPK_COLSUM_BIAS unset -> "exact": the one-launch kernel that adds in
+        the order of torch's reduce_kernel and so leaves torch's bits; shapes
+        or devices outside the ported configuration run torch's reduction.
+    =0 -> "torch": torch's reduction everywhere (semaphore memset, 32 blocks
+        per strip and a global combine for 1.5 MB: ~16 us per bias).
+    =1 -> "fast": the older one-launch kernel with its own order.  Once in
+        some million elements it rounds to the neighbouring bf16, which is
+        enough to move a training run onto another trajectory."""
+    v = os.environ.get("OKTOPK_COLSUM_BIAS")
+    if v == "1":
+        return "fast"
+    if v == "0":
+        return "torch"
+    return "exact"
 
 
 def direct_grad_enabled() -> bool:
@@ -174,13 +194,11 @@ def linear_param_grads(gy, x, w, b, need_w=True, need_b=True, w_shared=False):
     from oktopk_amd import _hip_ops
 
     owner = (ws or bs)[1]
-    # Default: torch's own column reduction writes the bias slot, so every
-    # gradient is bit-identical to the zero + accumulate path.  The
-    # one-launch column-sum kernel (3-4x faster per call) sums in another
-    # order; once in some million elements that rounds to the neighbouring
-    # bf16, which is enough to move a training run onto another trajectory,
-    # so it is opt-in like the unbound kernel path (OKTOPK_COLSUM_BIAS=1).
-    bias_kernel = os.environ.get("OKTOPK_COLSUM_BIAS", "0") == "1"
+    # Every gradient stays bit-identical to the zero + accumulate path: the
+    # default bias reduction is the one-launch kernel in torch's summation
+    # order (bias_grad_mode above; "fast" is the opt-in that is not).
+    mode = bias_grad_mode()
+    bias_kernel, bias_exact = mode == "fast", mode == "exact"
     keys = [id(p) for p, s in ((w, ws), (b, bs)) if s is not None]
     accumulate = all(k in owner.written for k in keys)
     if not accumulate and any(k in owner.written for k in keys):
@@ -189,11 +207,12 @@ def linear_param_grads(gy, x, w, b, need_w=True, need_b=True, w_shared=False):
                                       id(w) in owner.written, False)
         if bs is not None:
             _hip_ops.linear_bwd_into(gy, x, w, None, bs[0],
-                                     id(b) in owner.written, bias_kernel)
+                                     id(b) in owner.written, bias_kernel,
+                                     bias_exact)
     else:
         gx = _hip_ops.linear_bwd_into(gy, x, w, ws[0] if ws else None,
                                       bs[0] if bs else None, accumulate,
-                                      bias_kernel)
+                                      bias_kernel, bias_exact)
     owner.written.update(keys)
     gw = gy2.t() @ x2 if (need_w and ws is None) else None
     gb = gy2.sum(0) if (need_b and b is not None and bs is None) else None
@@ -271,9 +290,11 @@ class ColsumLinear(torch.nn.Linear):
     kernel with three launches (zeros, fp32-atomics kernel, cast) and its
     result still went through autograd's accumulate add, so it never tested
     whether removing kernels pays.  The switch now selects the one-launch
-    kernel, in the bound node too; it stays off by default because its
-    summation order differs from torch's in rare last-bit roundings
-    (profiles/README.md r03)."""
+    kernel, in the bound node too; it is opt-in because its summation
+    order differs from torch's in rare last-bit roundings
+    (profiles/README.md r03).  The bound node's default is since r07 the
+    one-launch kernel that follows torch's order (bias_grad_mode), which
+    takes the launches away without moving a bit."""
 
     def forward(self, x):
         if (x.is_cuda and x.dtype == torch.bfloat16

@@ -35,6 +35,7 @@ __all__ = [
     "pack_regions",
     "unpack_segments",
     "unpack_scatter_add_",
+    "colsum_torch_order",
 ]
 
 
@@ -423,3 +424,57 @@ def sumsq_into_(acc: torch.Tensor, t: torch.Tensor) -> None:
 
 def l2norm(t: torch.Tensor) -> float:
     return float(t.reshape(-1).norm(p=2).item())
+
+
+def colsum_torch_order(x: torch.Tensor, bh: int = 2, ctas: int = 32,
+                       vt0: int = 4) -> torch.Tensor:
+    """fp32 column sum of x [R, C] in the order torch's GPU reduction
+    (ATen/native/cuda/Reduce.cuh, reduce over the slow dimension) adds it:
+    the association tree native colsum_bf16_into_exact reproduces.
+
+    bh: block height, ctas: blocks per output, vt0: accumulators per thread.
+    Defaults are torch's configuration for bf16 [1024, 768 | 2304 | 3072] on
+    a 256-CU device; bh = 1, ctas = 1 stands for "rows not split over
+    threadIdx.y".  All adds are plain fp32, every accumulator starts at +0:
+      * lane l = ty + by*bh (ty < bh, by < ctas) takes rows l, l + bh*ctas,
+        ...; its k-th row goes to accumulator k mod vt0;
+      * T(l) = ((A0 + A1) + A2) + ... ;
+      * P(by): tree over ty, T[ty] += T[ty + off] for off = bh/2 ... 1;
+      * ctas > 1: G(ty) = ((0 + P(ty)) + P(ty + bh)) + ..., then the same
+        tree over G.
+    Returns the fp32 sum; the kernel rounds it once to bf16."""
+    assert x.dim() == 2 and bh >= 1 and ctas >= 1 and vt0 >= 1
+    assert bh & (bh - 1) == 0, "bh is a power of two"
+    xf = x.detach().float().cpu()
+    R, C = xf.shape
+    zero = torch.zeros(C, dtype=torch.float32)
+    step = bh * ctas
+
+    def tree(vals):
+        vals = list(vals)
+        off = len(vals) // 2
+        while off > 0:
+            for ty in range(off):
+                vals[ty] = vals[ty] + vals[ty + off]
+            off //= 2
+        return vals[0]
+
+    T = []
+    for lane in range(step):
+        acc = [zero.clone() for _ in range(vt0)]
+        for k, r in enumerate(range(lane, R, step)):
+            acc[k % vt0] = acc[k % vt0] + xf[r]
+        t = acc[0]
+        for a in acc[1:]:
+            t = t + a
+        T.append(t)
+    P = [tree(T[by * bh:(by + 1) * bh]) for by in range(ctas)]
+    if ctas == 1:
+        return P[0]
+    G = []
+    for ty in range(bh):
+        g = zero.clone()
+        for j in range(ty, ctas, bh):
+            g = g + P[j]
+        G.append(g)
+    return tree(G)

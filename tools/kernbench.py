@@ -53,18 +53,21 @@ def timeit_graph(fn, reps=100, replays=5):
 
 
 def colsum_rows():
-    """Bias-gradient column sum at the BERT-base shapes: the one-launch
-    kernel that stores into an (unaligned) gradient slot vs torch's sum(0)
-    into a preallocated output."""
+    """Bias-gradient column sum at the BERT-base shapes: the two one-launch
+    kernels that store into an (unaligned) gradient slot (colsum_into: own
+    order; colsum_exact: torch's order, torch's bits) vs torch's sum(0) into
+    a preallocated output."""
     g = torch.Generator().manual_seed(1)
     rows = []
-    for C in (768, 3072, 30522):
+    for C in (768, 2304, 3072, 30522):
         gy = torch.randn(1024, C, generator=g).bfloat16().cuda()
         dst = torch.empty(C + 8, dtype=torch.bfloat16, device="cuda")[3:3 + C]
         out = torch.empty(C, dtype=torch.bfloat16, device="cuda")
         nbytes = 2 * 1024 * C
         for name, fn in (
             (f"colsum_into [1024,{C}]", lambda: H.colsum_bf16_into(gy, dst, False)),
+            (f"colsum_exact [1024,{C}]",
+             lambda: H.colsum_bf16_into_exact(gy, dst, False)),
             (f"torch sum(0) [1024,{C}]", lambda: torch.sum(gy, 0, out=out)),
         ):
             ms = timeit_graph(fn) * 1000
