@@ -184,7 +184,9 @@ class AllReducer:
         ok = self.cfg.oktopk
         fused_ef = comp in ("oktopk", "topkAopt", "topkSA", "gaussiankSA") or (
             self.cfg.gaussian_device_select
-            and comp in ("gaussiank", "gaussiankconcat"))
+            and comp in ("gaussiank", "gaussiankconcat")) or (
+            self.cfg.device_exact_topk
+            and comp in ("topkA", "topkA2", "gtopk"))
         if grad_src is not None and not (
             fused_ef and st.counter >= ok.dense_warmup_iters
         ):
@@ -297,6 +299,24 @@ class AllReducer:
         idx, val, _chosen, _cnt, tau, _tau0, _mean, _std = \
             ops.gaussian_select_ef(t, st.residual, grad, self.cfg.density, k)
         return idx, val, tau
+
+    def _exact_topk_select(self, t: torch.Tensor, st: TensorState, k: int):
+        """compress_org (VGG/compression.py:37-62): EF restore, exact top-k,
+        residual keeps the unselected part.  Returns (idx int32, val); t may
+        or may not hold the restored values afterwards (callers overwrite
+        it).  With device_exact_topk it is one ops.topk_select_ef call —
+        fused bf16 upcast of grad_src, idx ascending, t not written."""
+        if self.cfg.device_exact_topk:
+            grad = st.grad_src.reshape(-1) if st.grad_src is not None else None
+            st.grad_src = None
+            return ops.topk_select_ef(t, st.residual, grad, k)[:2]
+        t.add_(st.residual)
+        topv = torch.topk(t.abs(), k, sorted=False)
+        idx = topv.indices.to(torch.int32)
+        val = t[topv.indices]
+        st.residual.copy_(t)
+        ops.zero_at_(st.residual, idx)
+        return idx, val
 
     def get_current_density(self) -> float:
         """Per-epoch density schedule (reference get_current_density,
@@ -953,12 +973,7 @@ class AllReducer:
         s0 = time.perf_counter()
         # compress_org semantics (VGG/compression.py:37-62): EF restore, exact
         # top-k, residual keeps the unselected part.
-        t.add_(st.residual)
-        topv = torch.topk(t.abs(), k, sorted=False)
-        idx = topv.indices.to(torch.int32)
-        val = t[topv.indices]
-        st.residual.copy_(t)
-        ops.zero_at_(st.residual, idx)
+        idx, val = self._exact_topk_select(t, st, k)
         self._time(name, "compress", time.perf_counter() - s0)
 
         s1 = time.perf_counter()
@@ -974,11 +989,15 @@ class AllReducer:
         result.div_(P)
         if second_topk and P > 1:
             # topkA2: truncate the merged result to k again (VGG/allreducer.py:519-525)
-            top2 = torch.topk(result.abs(), k, sorted=False)
-            keep = top2.indices
-            vals = result[keep]
-            result.zero_()
-            result[keep] = vals
+            if self.cfg.device_exact_topk:
+                keep, vals = ops.topk_select(result, k)[:2]
+                ops.fill_sparse_scaled_(result, keep, vals, 1.0)
+            else:
+                top2 = torch.topk(result.abs(), k, sorted=False)
+                keep = top2.indices
+                vals = result[keep]
+                result.zero_()
+                result[keep] = vals
         self._time(name, "merge", time.perf_counter() - s2)
         return result
 
@@ -1308,12 +1327,7 @@ class AllReducer:
         k = self._k(n)
 
         s0 = time.perf_counter()
-        t.add_(st.residual)
-        topv = torch.topk(t.abs(), k, sorted=False)
-        idx = topv.indices.to(torch.int32)
-        val = t[topv.indices]
-        st.residual.copy_(t)
-        ops.zero_at_(st.residual, idx)
+        idx, val = self._exact_topk_select(t, st, k)
         self._time(name, "compress", time.perf_counter() - s0)
 
         s1 = time.perf_counter()
@@ -1339,12 +1353,22 @@ class AllReducer:
                                             dtype=torch.int32, device=comm.device)
                         comm.irecv(other, src=send_rank, tag=7).wait()
                         o_idx, o_val = self._unpack(other, [k])
-                        merged = torch.zeros(n, dtype=t.dtype, device=t.device)
-                        ops.scatter_add_(merged, cur_idx.to(t.device), cur_val.to(t.device))
-                        ops.scatter_add_(merged, o_idx.to(t.device), o_val.to(t.device))
-                        topm = torch.topk(merged.abs(), k, sorted=False)
-                        cur_idx = comm.to_comm(topm.indices.to(torch.int32))
-                        cur_val = comm.to_comm(merged[topm.indices])
+                        if self.cfg.device_exact_topk:
+                            # both packets are ascending: merge the 2k
+                            # entries directly, nothing sized by n
+                            m_idx, m_val = ops.sparse_merge_topk(
+                                cur_idx.to(t.device), cur_val.to(t.device),
+                                o_idx.to(t.device).contiguous(),
+                                o_val.to(t.device).contiguous(), k)
+                            cur_idx = comm.to_comm(m_idx)
+                            cur_val = comm.to_comm(m_val)
+                        else:
+                            merged = torch.zeros(n, dtype=t.dtype, device=t.device)
+                            ops.scatter_add_(merged, cur_idx.to(t.device), cur_val.to(t.device))
+                            ops.scatter_add_(merged, o_idx.to(t.device), o_val.to(t.device))
+                            topm = torch.topk(merged.abs(), k, sorted=False)
+                            cur_idx = comm.to_comm(topm.indices.to(torch.int32))
+                            cur_val = comm.to_comm(merged[topm.indices])
                     elif rank == send_rank:
                         comm.isend(self._pack(cur_idx, cur_val),
                                    dst=recv_rank, tag=7).wait()
@@ -1369,7 +1393,11 @@ class AllReducer:
         # locally-selected value from the residual; add back those that did
         # NOT make the global top-k (reference add_residuals,
         # VGG/compression.py:151-160 called at VGG/allreducer.py:529).
-        member = ops.isin_sorted(idx, g_idx.to(t.device).long().sort().values.to(torch.int32))
+        if self.cfg.device_exact_topk:  # packets are ascending already
+            g_sorted = g_idx.to(t.device).contiguous()
+        else:
+            g_sorted = g_idx.to(t.device).long().sort().values.to(torch.int32)
+        member = ops.isin_sorted(idx, g_sorted)
         lost = ~member
         if lost.any():
             ops.scatter_add_(st.residual, idx[lost], val[lost])

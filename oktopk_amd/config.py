@@ -105,6 +105,22 @@ class EngineConfig:
     # level timings against the host composition are in profiles/README.md;
     # default off until a multi-GPU step time is measured.
     gaussian_device_select: bool = False
+    # Device-resident exact top-k for topkA / topkA2 / gtopk: the local
+    # selection is one ops.topk_select_ef call (EF restore with the first
+    # radix-histogram level fused in, two more levels, a (gt, eq) count and
+    # an ascending write that also zeroes the residual; one 16-byte
+    # readback) in place of add_ + torch.topk + gather + residual copy +
+    # zero_at_; topkA2's second truncation is ops.topk_select; each gtopk
+    # tree round merges with ops.sparse_merge_topk (work sized by the two
+    # k-entry packets) in place of zeros(n) + two scatters + torch.topk over
+    # n.  With it on, the three modes also take the fused bf16 grad_src
+    # upcast.  Same wire format, packet size and tree schedule; ties at the
+    # k-th magnitude go to the lowest index where torch.topk leaves the
+    # choice unspecified.  Kernel-level timings against the torch
+    # composition are in profiles/README.md; whether it shortens a real
+    # multi-GPU step is unmeasured (default off; flip only after the
+    # multi-GPU win is measured).
+    device_exact_topk: bool = False
     # EPS oracle (reference settings.PROFILING_NORM): when on, a dense
     # allreduce runs alongside the sparse one and the relative L2 error of the
     # sparse result is recorded.

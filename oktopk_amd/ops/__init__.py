@@ -112,6 +112,59 @@ def gaussian_select_ef(t: torch.Tensor, residual: torch.Tensor, grad,
             float(mean), float(std))
 
 
+def _check_select_args(name: str, t: torch.Tensor, k: int, *same) -> None:
+    if int(k) < 1:
+        raise ValueError(f"{name}: k must be >= 1")
+    if t.dtype != torch.float32 or t.dim() != 1 or t.numel() < 1:
+        raise TypeError(f"{name}: needs a non-empty 1-D fp32 tensor")
+    for x in same:
+        if x is not None and (x.device != t.device or x.numel() != t.numel()):
+            raise TypeError(f"{name}: device or size mismatch")
+
+
+def topk_select(t: torch.Tensor, k: int):
+    """Exact top-k by magnitude: the min(k, n) largest |t| (abs bit
+    pattern), the tie class at the k-th magnitude filled from the lowest
+    index.  Returns (idx int32 ascending, val, tau); writes nothing."""
+    _check_select_args("topk_select", t, k)
+    idx, val, tau = _backend(t).topk_select(t, int(k))
+    return idx, val, float(tau)
+
+
+def topk_select_ef(t: torch.Tensor, residual: torch.Tensor, grad, k: int):
+    """topk_select over restored = float(grad)+residual (grad bf16) or
+    t+residual, fused with the residual update: residual = restored with
+    +0.0 at the selected positions; t is NOT written.  Returns (idx int32
+    ascending, val, tau)."""
+    _check_select_args("topk_select_ef", t, k, residual, grad)
+    if residual.dtype != torch.float32:
+        raise TypeError("topk_select_ef: residual must be fp32")
+    if grad is not None and grad.dtype != torch.bfloat16:
+        raise TypeError("topk_select_ef: grad must be bf16 (or None)")
+    idx, val, tau = _backend(t).topk_select_ef(t, residual, grad, int(k))
+    return idx, val, float(tau)
+
+
+def sparse_merge_topk(a_idx: torch.Tensor, a_val: torch.Tensor,
+                      b_idx: torch.Tensor, b_val: torch.Tensor, k: int):
+    """Top-k of a + b for two sparse vectors (int32 indices ascending and
+    unique, fp32 values; either may be empty): union over indices, values
+    summed where both hold one, the min(k, |union|) largest |v| kept with
+    topk_select's tie rule.  Returns (idx ascending, val).  Work is
+    O((|a|+|b|) log), independent of the dense length."""
+    if int(k) < 1:
+        raise ValueError("sparse_merge_topk: k must be >= 1")
+    for i, v in ((a_idx, a_val), (b_idx, b_val)):
+        if (i.dtype != torch.int32 or v.dtype != torch.float32
+                or i.dim() != 1 or i.shape != v.shape):
+            raise TypeError("sparse_merge_topk: needs 1-D (int32 idx, fp32 "
+                            "val) pairs of equal length")
+        if i.device != a_idx.device or v.device != a_idx.device:
+            raise TypeError("sparse_merge_topk: device mismatch")
+    return tuple(_backend(a_val).sparse_merge_topk(a_idx, a_val, b_idx, b_val,
+                                                   int(k)))
+
+
 def scatter_add_(dest: torch.Tensor, idx: torch.Tensor, val: torch.Tensor) -> torch.Tensor:
     return _backend(dest).scatter_add_(dest, idx, val)
 

@@ -95,6 +95,21 @@ void launch_gauss_count(const float*, int64_t, const float*, int64_t, int, int*,
                         hipStream_t);
 void launch_gauss_decide(const int*, int, int64_t, const float*, double*,
                          hipStream_t);
+// topk_select.hip
+void launch_tk_ef_hist(const float*, float*, const void*, int64_t, unsigned int*,
+                       hipStream_t);
+void launch_tk_hist(const void*, int64_t, int, const uint32_t*, int, int, int,
+                    unsigned int*, hipStream_t);
+void launch_tk_pick(unsigned int*, int, int, uint32_t*, uint32_t, int,
+                    hipStream_t);
+void launch_tk_count(const void*, int64_t, int, int64_t, int, const uint32_t*,
+                     int*, hipStream_t);
+void launch_tk_write(const void*, float*, int64_t, int, int64_t, int,
+                     const uint32_t*, const int*, const int*, const int32_t*,
+                     const float*, int32_t*, float*, int, hipStream_t);
+void launch_tk_merge_slots(const int32_t*, const float*, int, const int32_t*,
+                           const float*, int, uint32_t*, int32_t*, float*, int*,
+                           hipStream_t);
 int wire_max_segments();
 void launch_wire_cuts(const int32_t*, int, const int64_t*, int, int, int*,
                       hipStream_t);
@@ -349,6 +364,159 @@ gaussian_select_ef(torch::Tensor t, torch::Tensor residual,
     auto out = compact_finish(residual, tau, g, counts, chosen, total);
     return std::make_tuple(out[0], out[1], (int64_t)chosen, total, tau, rp[3],
                            rp[4], rp[5]);
+}
+
+// Exact-k select over `len` 32-bit words (topk_select.hip): fp32 values
+// keyed by |x| bits, or ready-made keys (keymode).  `hist` holds level 1's
+// bins when the caller's fused pass already counted them (level1_done).
+// Every launch reads tau / need from the device state record; nothing is
+// read back here.  Fills out_idx / out_val (kout entries, ascending).
+static torch::Tensor tk_select_run(const void* words, int64_t len, int64_t kout,
+                                   bool keymode, float* zero_dst,
+                                   const int32_t* uidx, const float* uval,
+                                   torch::Tensor hist, bool level1_done,
+                                   torch::Tensor& out_idx,
+                                   torch::Tensor& out_val) {
+    auto i32 = hist.options().dtype(torch::kInt32);
+    auto state = torch::empty({4}, i32);
+    auto* sp = reinterpret_cast<uint32_t*>(state.data_ptr<int>());
+    auto* hp = reinterpret_cast<unsigned int*>(hist.data_ptr<int>());
+    auto stream = cur_stream();
+    const int shifts[3] = {21, 10, 0};
+    const int nbins[3] = {2048, 2048, 1024};
+    for (int lvl = 0; lvl < 3; ++lvl) {
+        if (!(lvl == 0 && level1_done))
+            launch_tk_hist(words, len, keymode, sp, lvl == 0, shifts[lvl],
+                           nbins[lvl], hp, stream);
+        launch_tk_pick(hp, nbins[lvl], shifts[lvl], sp, (uint32_t)kout,
+                       lvl == 0, stream);
+    }
+    auto g = compact_geom(len);
+    const int nw = g.nblocks * 4;
+    auto counts = torch::empty({(int64_t)2 * nw}, i32);
+    auto offs = torch::empty({(int64_t)2 * nw}, i32);
+    launch_tk_count(words, len, keymode, g.chunk, g.nblocks, sp,
+                    counts.data_ptr<int>(), stream);
+    launch_scan_offsets(counts.data_ptr<int>(), nw, offs.data_ptr<int>(), stream);
+    launch_scan_offsets(counts.data_ptr<int>() + nw, nw,
+                        offs.data_ptr<int>() + nw, stream);
+    launch_tk_write(words, zero_dst, len, keymode, g.chunk, g.nblocks, sp,
+                    offs.data_ptr<int>(), offs.data_ptr<int>() + nw, uidx, uval,
+                    out_idx.data_ptr<int32_t>(), out_val.data_ptr<float>(),
+                    (int)kout, stream);
+    return state;
+}
+
+static double tk_state_tau(const torch::Tensor& state) {
+    auto sh = state.cpu();
+    union { uint32_t u; float f; } c;
+    c.u = (uint32_t)sh.data_ptr<int>()[0];
+    return (double)c.f;
+}
+
+// Exact top-k by magnitude with the lowest-index tie rule; returns (idx
+// int32 ascending, val, tau).  Writes nothing but its outputs.
+static std::tuple<torch::Tensor, torch::Tensor, double> topk_select(
+    torch::Tensor t, int64_t k) {
+    check_f32_1d(t, "t");
+    int64_t n = t.numel();
+    TORCH_CHECK(k >= 1, "k must be >= 1");
+    TORCH_CHECK(n >= 1, "topk_select on empty tensor");
+    TORCH_CHECK(n < ((int64_t)1 << 31), "topk_select needs n < 2^31");
+    const at::cuda::CUDAGuard guard(t.device());
+    int64_t kout = k < n ? k : n;
+    auto idx = torch::empty({kout}, t.options().dtype(torch::kInt32));
+    auto val = torch::empty({kout}, t.options());
+    auto hist = torch::zeros({2048}, t.options().dtype(torch::kInt32));
+    auto state = tk_select_run(t.data_ptr<float>(), n, kout, false, nullptr,
+                               nullptr, nullptr, hist, false, idx, val);
+    return std::make_tuple(idx, val, tk_state_tau(state));
+}
+
+// topk_select over restored = float(grad) + residual (or t + residual),
+// with the EF restore fused into the first histogram level and the residual
+// zeroed at the selection by the write pass.  t is not written.
+static std::tuple<torch::Tensor, torch::Tensor, double> topk_select_ef(
+    torch::Tensor t, torch::Tensor residual, c10::optional<torch::Tensor> grad,
+    int64_t k) {
+    check_f32_1d(t, "t");
+    check_f32_1d(residual, "residual");
+    int64_t n = t.numel();
+    TORCH_CHECK(residual.numel() == n, "residual size mismatch");
+    TORCH_CHECK(residual.device() == t.device(), "residual device mismatch");
+    TORCH_CHECK(k >= 1, "k must be >= 1");
+    TORCH_CHECK(n >= 1, "topk_select_ef on empty tensor");
+    TORCH_CHECK(n < ((int64_t)1 << 31), "topk_select_ef needs n < 2^31");
+    const at::cuda::CUDAGuard guard(t.device());
+    const void* gp = nullptr;
+    if (grad.has_value()) {
+        auto& gt = grad.value();
+        TORCH_CHECK(gt.is_cuda() && gt.device() == t.device() &&
+                        gt.scalar_type() == torch::kBFloat16 &&
+                        gt.is_contiguous() && gt.numel() == n,
+                    "grad must be contiguous GPU bf16 of same numel");
+        gp = gt.data_ptr();
+    }
+    int64_t kout = k < n ? k : n;
+    auto idx = torch::empty({kout}, t.options().dtype(torch::kInt32));
+    auto val = torch::empty({kout}, t.options());
+    auto hist = torch::zeros({2048}, t.options().dtype(torch::kInt32));
+    float* rp = residual.data_ptr<float>();
+    launch_tk_ef_hist(t.data_ptr<float>(), rp, gp, n,
+                      reinterpret_cast<unsigned int*>(hist.data_ptr<int>()),
+                      cur_stream());
+    auto state = tk_select_run(rp, n, kout, false, rp, nullptr, nullptr, hist,
+                               true, idx, val);
+    return std::make_tuple(idx, val, tk_state_tau(state));
+}
+
+// Top-k of the sum of two sparse vectors (ascending unique indices): slot
+// layout + the same exact-k select over the slot keys.  Sized by
+// |a| + |b| only.  One 4-byte readback (the duplicate count), and none when
+// one list alone already holds k entries.
+static std::vector<torch::Tensor> sparse_merge_topk(
+    torch::Tensor a_idx, torch::Tensor a_val, torch::Tensor b_idx,
+    torch::Tensor b_val, int64_t k) {
+    check_i32_1d(a_idx, "a_idx");
+    check_f32_1d(a_val, "a_val");
+    check_i32_1d(b_idx, "b_idx");
+    check_f32_1d(b_val, "b_val");
+    TORCH_CHECK(a_idx.numel() == a_val.numel() && b_idx.numel() == b_val.numel(),
+                "idx / val length mismatch");
+    TORCH_CHECK(a_idx.device() == a_val.device() &&
+                    b_idx.device() == a_val.device() &&
+                    b_val.device() == a_val.device(),
+                "sparse_merge_topk: device mismatch");
+    TORCH_CHECK(k >= 1, "k must be >= 1");
+    int64_t na = a_idx.numel(), nb = b_idx.numel();
+    int64_t total = na + nb;
+    TORCH_CHECK(total < ((int64_t)1 << 31), "sparse_merge_topk: lists too long");
+    const at::cuda::CUDAGuard guard(a_val.device());
+    auto i32 = a_val.options().dtype(torch::kInt32);
+    if (total == 0)
+        return {torch::empty({0}, i32), torch::empty({0}, a_val.options())};
+    auto ukey = torch::empty({total}, i32);
+    auto uidx = torch::empty({total}, i32);
+    auto uval = torch::empty({total}, a_val.options());
+    // [0, 2048) histogram bins, [2048] duplicate count
+    auto work = torch::zeros({2049}, i32);
+    launch_tk_merge_slots(a_idx.data_ptr<int32_t>(), a_val.data_ptr<float>(),
+                          (int)na, b_idx.data_ptr<int32_t>(),
+                          b_val.data_ptr<float>(), (int)nb,
+                          reinterpret_cast<uint32_t*>(ukey.data_ptr<int>()),
+                          uidx.data_ptr<int32_t>(), uval.data_ptr<float>(),
+                          work.data_ptr<int>() + 2048, cur_stream());
+    int64_t kout = k;
+    if (k > (na > nb ? na : nb)) {  // the union may be smaller than k
+        int64_t m = total - work.narrow(0, 2048, 1).cpu().item<int>();
+        kout = k < m ? k : m;
+    }
+    auto idx = torch::empty({kout}, i32);
+    auto val = torch::empty({kout}, a_val.options());
+    tk_select_run(ukey.data_ptr<int>(), total, kout, true, nullptr,
+                  uidx.data_ptr<int32_t>(), uval.data_ptr<float>(),
+                  work.narrow(0, 0, 2048), false, idx, val);
+    return {idx, val};
 }
 
 static double kth_abs_value(torch::Tensor t, int64_t k) {
@@ -1252,6 +1420,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "chosen, count, tau, tau0, mean, std)",
           py::arg("t"), py::arg("residual"), py::arg("grad"),
           py::arg("density"), py::arg("k"));
+    m.def("topk_select", &topk_select,
+          "exact top-k by |t| (lowest-index ties); returns (idx, val, tau)",
+          py::arg("t"), py::arg("k"));
+    m.def("topk_select_ef", &topk_select_ef,
+          "fused EF restore(+bf16 upcast) + exact top-k; residual = restored "
+          "with the selection zeroed; returns (idx, val, tau)",
+          py::arg("t"), py::arg("residual"), py::arg("grad"), py::arg("k"));
+    m.def("sparse_merge_topk", &sparse_merge_topk,
+          "top-k of the sum of two ascending sparse vectors; returns (idx, val)",
+          py::arg("a_idx"), py::arg("a_val"), py::arg("b_idx"),
+          py::arg("b_val"), py::arg("k"));
     m.def("kth_abs_value", &kth_abs_value, "exact k-th largest |t| via radix select");
     m.def("scatter_add_", &scatter_add_, "dest[idx] += val");
     m.def("zero_at_", &zero_at_, "t[idx] = 0");

@@ -22,6 +22,9 @@ __all__ = [
     "count_multi_gt",
     "compact_adaptive",
     "gaussian_select_ef",
+    "topk_select",
+    "topk_select_ef",
+    "sparse_merge_topk",
     "scatter_add_",
     "zero_at_",
     "zero_at_masked_",
@@ -165,6 +168,81 @@ def gaussian_select_ef(t: torch.Tensor, residual: torch.Tensor, grad,
     tau = cand[chosen]
     idx, val = compact_gt(restored, tau)
     return idx, val, chosen, counts[chosen], tau, tau0, mean, std
+
+
+def _abs_bits(x: torch.Tensor) -> torch.Tensor:
+    """|x| as its int32 bit pattern: nonnegative floats order as integers."""
+    return x.contiguous().view(torch.int32) & 0x7FFFFFFF
+
+
+def topk_select(t: torch.Tensor, k: int):
+    """Exact top-k by magnitude with a defined tie rule: the min(k, n)
+    elements of largest |t| (compared on the abs bit pattern); with tau the
+    k-th largest magnitude, everything above tau is taken and the tie class
+    |t| == tau is filled from the lowest index up to exactly k.  Returns
+    (idx int32 ascending, val, tau); writes nothing.
+
+    Replaces torch.topk + gather in compress_org, VGG/compression.py:37-62."""
+    flat = t.reshape(-1)
+    n = flat.numel()
+    if k < 1 or n < 1:
+        raise ValueError("topk_select: k and n must be >= 1")
+    k = min(int(k), n)
+    bits = _abs_bits(flat)
+    tau_bits = torch.kthvalue(bits, n - k + 1).values
+    gt = bits > tau_bits
+    eq = bits == tau_bits
+    need = k - int(gt.sum().item())
+    sel = gt | (eq & (torch.cumsum(eq, 0) <= need))
+    idx = sel.nonzero(as_tuple=False).reshape(-1)
+    tau = float(tau_bits.reshape(1).view(torch.float32).item())
+    return idx.to(torch.int32), flat[idx], tau
+
+
+def topk_select_ef(t: torch.Tensor, residual: torch.Tensor, grad, k: int):
+    """topk_select over restored = float(grad) + residual (grad bf16) or
+    t + residual, with the compress_org residual update fused in: on return
+    residual holds restored with +0.0 at the selected positions.  t is NOT
+    written (as in gaussian_select_ef).  Returns (idx, val, tau)."""
+    if residual.numel() != t.numel():
+        raise ValueError("topk_select_ef: residual size mismatch")
+    if grad is not None:
+        restored = grad.reshape(-1).to(t.dtype) + residual
+    else:
+        restored = t.reshape(-1) + residual
+    idx, val, tau = topk_select(restored, k)
+    residual.copy_(restored)
+    residual[idx.long()] = 0.0
+    return idx, val, tau
+
+
+def sparse_merge_topk(a_idx: torch.Tensor, a_val: torch.Tensor,
+                      b_idx: torch.Tensor, b_val: torch.Tensor, k: int):
+    """Top-k of the sum of two sparse vectors (ascending unique int32
+    indices) without densifying: the union over indices, a_val + b_val where
+    both hold an index (a sum of exactly 0 stays in the union), truncated to
+    the min(k, |union|) largest |v| with topk_select's lowest-index tie
+    rule.  Returns (idx ascending, val).
+
+    Replaces the zeros(n) + two scatters + torch.topk of the gTopK tree
+    merge, VGG/allreducer.py:116-150."""
+    if k < 1:
+        raise ValueError("sparse_merge_topk: k must be >= 1")
+    idx = torch.cat([a_idx, b_idx])
+    val = torch.cat([a_val, b_val])
+    m = idx.numel()
+    if m == 0:
+        return idx, val
+    order = torch.argsort(idx, stable=True)  # a before b where equal
+    si, sv = idx[order], val[order]
+    first = torch.ones(m, dtype=torch.bool, device=idx.device)
+    first[1:] = si[1:] != si[:-1]
+    has_twin = torch.zeros_like(first)
+    has_twin[:-1] = ~first[1:]
+    summed = torch.where(has_twin, sv + torch.roll(sv, -1), sv)
+    u_idx, u_val = si[first], summed[first]
+    pos, out_val, _ = topk_select(u_val, k)
+    return u_idx[pos.long()], out_val
 
 
 def scatter_add_(dest: torch.Tensor, idx: torch.Tensor, val: torch.Tensor) -> torch.Tensor:

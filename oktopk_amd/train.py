@@ -49,6 +49,10 @@ def build_argparser() -> argparse.ArgumentParser:
     p.add_argument("--device-wire", action="store_true",
                    help="oktopk device-side wire codec (region pack + fused "
                         "unpack-reduce kernels)")
+    p.add_argument("--device-exact-topk", action="store_true",
+                   help="topkA/topkA2/gtopk: device-resident exact top-k "
+                        "selection and sparse tree merge instead of "
+                        "torch.topk over the whole gradient")
     p.add_argument("--gaussian-device-select", action="store_true",
                    help="gaussiank/gaussiankconcat/gaussiankSA: device-"
                         "resident threshold selection (fused moments + ppf "
@@ -99,6 +103,7 @@ def main(argv=None) -> int:
                      balanced_allgather=args.balanced_allgather,
                      device_wire=args.device_wire,
                      gaussian_device_select=args.gaussian_device_select,
+                     device_exact_topk=args.device_exact_topk,
                      pipeline_chunks=args.pipeline_chunks)
     if args.dense_warmup is not None:
         overrides["dense_warmup_iters"] = args.dense_warmup

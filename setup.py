@@ -20,6 +20,7 @@ setup(
                 "oktopk_amd/ops/csrc/bindings.cpp",
                 "oktopk_amd/ops/csrc/kernels.hip",
                 "oktopk_amd/ops/csrc/gauss_select.hip",
+                "oktopk_amd/ops/csrc/topk_select.hip",
                 "oktopk_amd/ops/csrc/wire_codec.hip",
                 "oktopk_amd/ops/csrc/direct_grad.hip",
                 "oktopk_amd/ops/csrc/ln_bwd.hip",

@@ -31,6 +31,9 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--compressors", default=",".join(COMPRESSORS))
+    ap.add_argument("--device-exact-topk", action="store_true",
+                    help="topkA/topkA2/gtopk select and merge with the exact-k "
+                         "HIP ops (EngineConfig.device_exact_topk)")
     args = ap.parse_args()
 
     comm = init_from_env()
@@ -40,7 +43,8 @@ def main():
         if comp == "gtopk" and comm.size & (comm.size - 1):
             continue
         cfg = EngineConfig.preset("bert", compressor=comp, density=args.density,
-                                  dense_warmup_iters=0)
+                                  dense_warmup_iters=0,
+                                  device_exact_topk=args.device_exact_topk)
         tr = Trainer(args.model, batch_size=args.batch_size, seq_len=128,
                      comm=comm, cfg=cfg,
                      dtype="bf16" if torch.cuda.is_available() else "fp32")
@@ -67,7 +71,8 @@ def main():
             torch.cuda.empty_cache()
     if comm.rank == 0:
         print(f"# {args.model} bs{args.batch_size} density={args.density} "
-              f"P={comm.size} steps={args.steps}")
+              f"P={comm.size} steps={args.steps}"
+              + (" device_exact_topk" if args.device_exact_topk else ""))
         print(f"{'compressor':12s} {'ms/step':>9s}  phases(ms)")
         for comp, ms, ph in rows:
             pstr = " ".join(f"{k}={v:.2f}" for k, v in sorted(ph.items()))

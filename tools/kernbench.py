@@ -239,6 +239,100 @@ def gauss_rows(reps, sizes=(109_500_000, 25_000_000), density=0.001,
                       f"{ts[len(ts) // 2]:10.3f} {ts[0]:9.3f} {ts[-1]:9.3f}")
 
 
+def _alternate(arms, reset, reps):
+    """Each arm timed alone (reset, synchronise, host clock around call +
+    synchronise), the arms alternating inside one repeat loop; two warm-up
+    repeats.  Returns {name: sorted ms} and {name: last result}."""
+    times = {name: [] for name, _ in arms}
+    last = {}
+    for r in range(reps + 2):
+        for name, fn in arms:
+            reset()
+            torch.cuda.synchronize()
+            c0 = time.perf_counter()
+            last[name] = fn()
+            torch.cuda.synchronize()
+            if r >= 2:
+                times[name].append((time.perf_counter() - c0) * 1000)
+    return {k: sorted(v) for k, v in times.items()}, last
+
+
+def topk_rows(reps, sizes=(109_500_000, 336_000_000), density=0.001):
+    """Exact top-k ops (ops/csrc/topk_select.hip) against the torch
+    compositions the topkA / gtopk engine paths run without
+    device_exact_topk.  Select: add_ + torch.topk(|t|, k) + gather +
+    residual.copy_ + zero_at_ (plus the bf16 upcast copy_ in the bf16 rows)
+    against one topk_select_ef.  Merge: zeros(n) + two scatter_add_ +
+    torch.topk over n + gather against sparse_merge_topk on the two k-entry
+    packets.  Every arm ends in a host readback or an allocation, so each
+    call is timed alone; median and min..max over `reps` repeats."""
+    from oktopk_amd import ops
+
+    print(f"# exact top-k, density={density}, {reps} repeats/row")
+    print(f"{'path':44s} {'median ms':>10s} {'min ms':>9s} {'max ms':>9s}")
+
+    def show(label, n, ts):
+        print(f"{label:30s} n={n:<11d} {ts[len(ts) // 2]:10.3f} "
+              f"{ts[0]:9.3f} {ts[-1]:9.3f}")
+
+    def same_magnitudes(last):
+        # torch.topk may pick other members of the tie class at the k-th
+        # magnitude; the selected magnitudes are the same either way
+        a, b = (last[x][1].abs().sort().values for x in ("torch", "hip"))
+        assert torch.equal(a, b), "selections differ"
+
+    for n in sizes:
+        k = max(1, int(n * density))
+        g = torch.Generator(device="cuda").manual_seed(0)
+        t0 = torch.randn(n, device="cuda", generator=g)
+        r0 = torch.randn(n, device="cuda", generator=g) * 0.1
+        g16 = t0.to(torch.bfloat16)
+        t, r = t0.clone(), r0.clone()
+
+        def reset():
+            t.copy_(t0)
+            r.copy_(r0)
+
+        def torch_select(grad):
+            if grad is not None:
+                t.copy_(grad.to(t.dtype))
+            t.add_(r)
+            topv = torch.topk(t.abs(), k, sorted=False)
+            idx = topv.indices.to(torch.int32)
+            val = t[topv.indices]
+            r.copy_(t)
+            ops.zero_at_(r, idx)
+            return idx, val
+
+        for tag, grad in (("fp32", None), ("bf16", g16)):
+            times, last = _alternate(
+                (("torch", lambda: torch_select(grad)),
+                 ("hip", lambda: ops.topk_select_ef(t, r, grad, k)[:2])),
+                reset, reps)
+            same_magnitudes(last)
+            show(f"select {tag} torch 5-op", n, times["torch"])
+            show(f"select {tag} topk_select_ef", n, times["hip"])
+
+        a_idx, a_val, _ = ops.topk_select(t0, k)
+        b_idx, b_val, _ = ops.topk_select(r0, k)
+
+        def dense_merge():
+            merged = torch.zeros(n, dtype=t0.dtype, device="cuda")
+            ops.scatter_add_(merged, a_idx, a_val)
+            ops.scatter_add_(merged, b_idx, b_val)
+            topm = torch.topk(merged.abs(), k, sorted=False)
+            return topm.indices.to(torch.int32), merged[topm.indices]
+
+        times, last = _alternate(
+            (("torch", dense_merge),
+             ("hip", lambda: ops.sparse_merge_topk(a_idx, a_val, b_idx, b_val, k))),
+            lambda: None, reps)
+        same_magnitudes(last)
+        show("merge dense zeros+scatter+topk", n, times["torch"])
+        show("merge sparse_merge_topk", n, times["hip"])
+        del t0, r0, g16, t, r
+
+
 def sparse_step_rows(iters, density=0.001):
     """The optimizer tail at the 109.5 M flat scale with k = 0.1 %: the dense
     hand-over (zero fill + scatter + dense sum of squares + Adam over p, g,
@@ -304,9 +398,10 @@ def main():
     ap.add_argument("--iters", type=int, default=None,
                     help="calls per timed window (default 20; 1000 for the "
                          "microsecond-scale --only wire rows; repeats per "
-                         "row, default 15, for --only gauss)")
+                         "row, default 15, for --only gauss and topk)")
     ap.add_argument("--only", default="",
-                    choices=["", "colsum", "wire", "gauss", "sparse_step"],
+                    choices=["", "colsum", "wire", "gauss", "sparse_step",
+                             "topk"],
                     help="run just one group of rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -321,6 +416,9 @@ def main():
         return
     if args.only == "gauss":
         gauss_rows(args.iters or 15)
+        return
+    if args.only == "topk":
+        topk_rows(args.iters or 15)
         return
     args.iters = args.iters or 20
     g = torch.Generator().manual_seed(0)
