@@ -161,7 +161,8 @@ class AllReducer:
         compressor path supports it (one streaming pass saved).
 
         `sparse_ok`: the caller can consume a SparseGrad.  Where the path
-        taken ends in an ascending selection (the non-exact Ok-Topk tails)
+        taken ends in an ascending selection (the non-exact Ok-Topk tails;
+        with device_round2 every Ok-Topk tail outside the chunked engine)
         the result is then left in `self.sparse_result` and `tensor` is NOT
         written — no zero fill, no scatter; every other path densifies as
         usual and leaves `self.sparse_result` None for that step.
@@ -516,6 +517,7 @@ class AllReducer:
                 return result
             gidx, gval = idx, val
 
+        wire = None  # device_round2: the gathered buffer, still packed
         if P == 1:
             # no communication: the packed wire round-trip is pure overhead
             all_idx, all_val = gidx, gval
@@ -525,18 +527,42 @@ class AllReducer:
             pack = comm.to_comm(self._pack_one(gidx, gval, n))
             elem_counts = [int(x) for x in comm.allgather_sizes(gidx.numel(), comm.device)]
             buf, _ = comm.allgatherv(pack, sizes=[self._pack_ints(c) for c in elem_counts])
-            all_idx, all_val = ops.unpack_segments(buf.to(t.device), elem_counts,
-                                                   self._wire_bf16)
+            if ok.device_round2:
+                # the tail decodes the segments itself
+                wire = (buf.to(t.device), elem_counts)
+            else:
+                all_idx, all_val = ops.unpack_segments(
+                    buf.to(t.device), elem_counts, self._wire_bf16)
         else:
             pack = comm.to_comm(self._pack(gidx, gval))
             elem_counts = [int(x) for x in comm.allgather_sizes(gidx.numel(), comm.device)]
             buf, _ = comm.allgatherv(pack, sizes=[self._pack_ints(c) for c in elem_counts])
             all_idx, all_val = self._unpack(buf, elem_counts)
-        all_idx = all_idx.to(t.device)
-        all_val = all_val.to(t.device)
+        if wire is None:
+            all_idx = all_idx.to(t.device)
+            all_val = all_val.to(t.device)
         self._time(name, "allgather", time.perf_counter() - s3)
 
         s4 = time.perf_counter()
+        if ok.device_round2:
+            # --- 5'. global selection + residual credit in one op ---------
+            g_sel_idx, g_sel_val = self._round2_tail(
+                st, idx, k, exact,
+                pair=None if wire is not None else (all_idx, all_val),
+                wire=wire)
+            result = t
+            if self._sparse_ok:
+                # sparse hand-over on every iteration: the op's selection is
+                # ascending and unique on the exact iterations too, and
+                # _balanced_round2 returns global position order like the
+                # plain allgather.  No filter (tau < 0); 1.0 / P is 1.0 on
+                # the world-1 exact iteration.
+                self.sparse_result = SparseGrad(g_sel_idx, g_sel_val, 1.0 / P,
+                                                -1.0)
+            else:
+                ops.fill_sparse_scaled_(result, g_sel_idx, g_sel_val, 1.0 / P)
+            self._time(name, "merge", time.perf_counter() - s4)
+            return result
         if exact:
             kk = min(k, all_val.numel())
             if kk > 0:
@@ -587,6 +613,36 @@ class AllReducer:
             st.mask[g_sel_idx.long()] = True
             ops.zero_at_masked_(st.residual, idx, st.mask)
             st.mask[g_sel_idx.long()] = False  # cheap sparse reset
+
+    def _round2_tail(self, st: TensorState, idx: torch.Tensor, k: int,
+                     exact: bool, pair=None, wire=None):
+        """device_round2: the global selection over the gathered survivors
+        — `pair` = (all_idx, all_val), or `wire` = (allgathered buffer,
+        element counts) — and the residual credit, in one ops.round2_tail_ /
+        round2_tail_wire_ call; then the threshold bookkeeping of the host
+        composition.  An exact iteration keeps the k largest and takes
+        tau_global from the op (left as it is when nothing was gathered);
+        a threshold iteration keeps everything and runs the global feedback
+        controller (VGG/allreducer.py:1054-1057).  Returns (g_idx, g_val),
+        ascending; no n-sized mask is involved."""
+        ok = self.cfg.oktopk
+        kk = k if exact else None
+        if wire is not None:
+            g_idx, g_val, tau = ops.round2_tail_wire_(
+                st.residual, idx, wire[0], wire[1], self._wire_bf16, kk)
+        else:
+            g_idx, g_val, tau = ops.round2_tail_(
+                st.residual, idx, pair[0], pair[1], kk)
+        if exact:
+            if tau is not None:
+                st.tau_global = tau
+        else:
+            gsz = g_idx.numel()
+            if gsz < ok.global_lo_num * k // ok.global_lo_den:
+                st.tau_global /= ok.scale_global_increase
+            elif gsz > ok.global_hi_num * k // ok.global_hi_den:
+                st.tau_global *= ok.scale_global_decrease
+        return g_idx, g_val
 
     # -- stage-pipelined Ok-Topk (docs/overlap_design.md) ----------------
     def run_many(self, items: List[Tuple[str, torch.Tensor, Optional[torch.Tensor]]]) -> None:
@@ -796,6 +852,19 @@ class AllReducer:
         s4 = time.perf_counter()
         for c in parts:
             st, sl = c["st"], c["sl"]
+            if ok.device_round2:
+                if ok.device_wire:
+                    g_sel_idx, g_sel_val = self._round2_tail(
+                        st, c["idx"], c["k"], c["exact"],
+                        wire=(c["w_gather"].wait().to(dev), c["gsizes"]))
+                else:
+                    all_idx, all_val = self._unpack(c["w_gather"].wait(),
+                                                    c["gsizes"])
+                    g_sel_idx, g_sel_val = self._round2_tail(
+                        st, c["idx"], c["k"], c["exact"],
+                        pair=(all_idx.to(dev), all_val.to(dev)))
+                ops.fill_sparse_scaled_(sl, g_sel_idx, g_sel_val, 1.0 / P)
+                continue
             if ok.device_wire:
                 all_idx, all_val = ops.unpack_segments(
                     c["w_gather"].wait().to(dev), c["gsizes"], self._wire_bf16)
@@ -830,6 +899,12 @@ class AllReducer:
         st, sl = c["st"], c["sl"]
         idx, val, k = c["idx"], c["val"], c["k"]
         exact = it % ok.global_threshold_recompute_interval == 0 or st.tau_global <= 0.0
+        if exact and ok.device_round2:
+            # the gathered lists are the local selection
+            g_sel_idx, g_sel_val = self._round2_tail(st, idx, k, True,
+                                                     pair=(idx, val))
+            ops.fill_sparse_scaled_(sl, g_sel_idx, g_sel_val, 1.0)
+            return
         if exact:
             g_sel_idx, g_sel_val = idx, val
             kk = min(k, val.numel())

@@ -73,6 +73,22 @@ class OkTopkConfig:
     # multi-GPU step is unmeasured (default off; flip only after the
     # multi-GPU win is measured).
     device_wire: bool = False
+    # Device-side round-2 tail: everything after the sparse allgather —
+    # the global selection (every gathered entry, or on an exact-recompute
+    # iteration the k of largest magnitude) and the residual credit — is
+    # one ops.round2_tail_ / ops.round2_tail_wire_ call, in place of
+    # abs + torch.topk + .item() + two gathers and the n-element bool mask
+    # with its two index_puts.  The wire form (with device_wire, after the
+    # plain allgather) decodes the gathered buffer in the same kernel.  The
+    # selection comes back ascending on every iteration, so the sparse
+    # hand-over to clip / Adam also covers the exact iterations and
+    # balanced_allgather; TensorState.mask is never allocated.  Ties at the
+    # k-th magnitude go to the lowest gathered position where torch.topk
+    # leaves the choice unspecified.  Kernel-level timings against the torch
+    # composition are in profiles/README.md; whether it shortens a real
+    # multi-GPU step is unmeasured (default off; flip only after the
+    # multi-GPU win is measured).
+    device_round2: bool = False
 
 
 @dataclass

@@ -329,6 +329,62 @@ def unpack_scatter_add_(dest: torch.Tensor, buf: torch.Tensor, counts,
         dest, buf, counts, int(base), bool(wire_bf16))
 
 
+# -- Ok-Topk round-2 tail: global selection + residual credit ----------------
+
+def _check_round2_args(name: str, residual, idx, k, *i32f32) -> None:
+    if k is not None and int(k) < 1:
+        raise ValueError(f"{name}: k must be >= 1")
+    if residual.dtype != torch.float32 or residual.dim() != 1:
+        raise ValueError(f"{name}: residual must be a 1-D fp32 tensor")
+    if idx.dtype != torch.int32 or idx.dim() != 1:
+        raise ValueError(f"{name}: idx must be a 1-D int32 tensor")
+    for x, dt in i32f32:
+        if x.dtype != dt or x.dim() != 1:
+            raise ValueError(f"{name}: needs 1-D int32 index / wire words "
+                             "and fp32 values")
+    for x in (idx,) + tuple(x for x, _ in i32f32):
+        if x.device != residual.device:
+            raise ValueError(f"{name}: device mismatch")
+
+
+def round2_tail_(residual: torch.Tensor, idx: torch.Tensor,
+                 all_idx: torch.Tensor, all_val: torch.Tensor, k=None):
+    """Round-2 tail of Ok-Topk over the gathered survivors (all_idx int32
+    ascending and unique, all_val fp32) and the local selection idx (int32
+    ascending, unique).  k None, or nothing gathered: the selection is every
+    gathered entry, returned as passed in, tau None.  k given: the
+    min(k, S) largest |all_val| under topk_select's rule, g_idx ascending,
+    tau the k-th magnitude.  Either way residual[j] = +0.0 for every j in
+    both g_idx and idx and nothing else is written.  Returns (g_idx, g_val,
+    tau)."""
+    _check_round2_args("round2_tail_", residual, idx, k,
+                       (all_idx, torch.int32), (all_val, torch.float32))
+    if all_idx.numel() != all_val.numel():
+        raise ValueError("round2_tail_: all_idx / all_val length mismatch")
+    g_idx, g_val, tau = _backend(residual).round2_tail_(
+        residual, idx, all_idx, all_val, None if k is None else int(k))
+    return g_idx, g_val, None if tau is None else float(tau)
+
+
+def round2_tail_wire_(residual: torch.Tensor, idx: torch.Tensor,
+                      buf: torch.Tensor, counts, wire_bf16: bool, k=None):
+    """round2_tail_ with the gathered survivors given as the allgathered
+    wire buffer (`counts`: element counts per rank segment): bit-equal to
+    round2_tail_ over unpack_segments(buf, counts, wire_bf16), decoded in
+    the same kernels on the GPU.  With k=None the returned pair is the
+    unpacked lists."""
+    counts = [int(c) for c in counts]
+    _check_round2_args("round2_tail_wire_", residual, idx, k,
+                       (buf, torch.int32))
+    if any(c < 0 for c in counts) or sum(
+            _ref._wire_words(c, bool(wire_bf16)) for c in counts) > buf.numel():
+        raise ValueError("round2_tail_wire_: counts do not fit the buffer")
+    g_idx, g_val, tau = _wire_backend(residual, len(counts)).round2_tail_wire_(
+        residual, idx, buf, counts, bool(wire_bf16),
+        None if k is None else int(k))
+    return g_idx, g_val, None if tau is None else float(tau)
+
+
 def grad_clip_scale(t: torch.Tensor, max_norm: float) -> torch.Tensor:
     """Device-resident clip factor: min(1, max/(||t||+1e-6)) as a 1-elem
     tensor, no host sync (feeds fused_adam_'s gscale)."""

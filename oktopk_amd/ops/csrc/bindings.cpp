@@ -119,6 +119,15 @@ void launch_wire_unpack(const int32_t*, const int*, int, int, int, int32_t*,
                         float*, hipStream_t);
 void launch_wire_scatter_add(float*, int64_t, const int32_t*, const int*, int,
                              int, int64_t, int, hipStream_t);
+// round-2 tail (round2_tail.hip)
+void launch_r2_credit(const int32_t*, int, const int32_t*, int, float*, int64_t,
+                      hipStream_t);
+void launch_r2_wire_tail(const int32_t*, const int*, int, int, int, int32_t*,
+                         float*, const int32_t*, int, float*, int64_t,
+                         unsigned int*, hipStream_t);
+void launch_r2_write(const void*, const int32_t*, int64_t, int64_t, int,
+                     const uint32_t*, const int*, const int*, const int32_t*,
+                     int, float*, int64_t, int32_t*, float*, int, hipStream_t);
 }
 
 namespace {
@@ -371,12 +380,24 @@ gaussian_select_ef(torch::Tensor t, torch::Tensor residual,
 // bins when the caller's fused pass already counted them (level1_done).
 // Every launch reads tau / need from the device state record; nothing is
 // read back here.  Fills out_idx / out_val (kout entries, ascending).
+// With `r2` the write pass is the round-2 tail's (round2_tail.hip): it emits
+// (all_idx[pos], words[pos]) and credits the residual at the entries that
+// the local selection also holds.
+struct R2Write {
+    const int32_t* all_idx;
+    const int32_t* idx;
+    int m;
+    float* residual;
+    int64_t n;
+};
+
 static torch::Tensor tk_select_run(const void* words, int64_t len, int64_t kout,
                                    bool keymode, float* zero_dst,
                                    const int32_t* uidx, const float* uval,
                                    torch::Tensor hist, bool level1_done,
                                    torch::Tensor& out_idx,
-                                   torch::Tensor& out_val) {
+                                   torch::Tensor& out_val,
+                                   const R2Write* r2 = nullptr) {
     auto i32 = hist.options().dtype(torch::kInt32);
     auto state = torch::empty({4}, i32);
     auto* sp = reinterpret_cast<uint32_t*>(state.data_ptr<int>());
@@ -400,10 +421,17 @@ static torch::Tensor tk_select_run(const void* words, int64_t len, int64_t kout,
     launch_scan_offsets(counts.data_ptr<int>(), nw, offs.data_ptr<int>(), stream);
     launch_scan_offsets(counts.data_ptr<int>() + nw, nw,
                         offs.data_ptr<int>() + nw, stream);
-    launch_tk_write(words, zero_dst, len, keymode, g.chunk, g.nblocks, sp,
-                    offs.data_ptr<int>(), offs.data_ptr<int>() + nw, uidx, uval,
-                    out_idx.data_ptr<int32_t>(), out_val.data_ptr<float>(),
-                    (int)kout, stream);
+    if (r2 != nullptr)
+        launch_r2_write(words, r2->all_idx, len, g.chunk, g.nblocks, sp,
+                        offs.data_ptr<int>(), offs.data_ptr<int>() + nw,
+                        r2->idx, r2->m, r2->residual, r2->n,
+                        out_idx.data_ptr<int32_t>(), out_val.data_ptr<float>(),
+                        (int)kout, stream);
+    else
+        launch_tk_write(words, zero_dst, len, keymode, g.chunk, g.nblocks, sp,
+                        offs.data_ptr<int>(), offs.data_ptr<int>() + nw, uidx,
+                        uval, out_idx.data_ptr<int32_t>(),
+                        out_val.data_ptr<float>(), (int)kout, stream);
     return state;
 }
 
@@ -1103,6 +1131,95 @@ static torch::Tensor unpack_scatter_add_(torch::Tensor dest, torch::Tensor buf,
     return dest;
 }
 
+// ---------------------------------------------------------------------------
+// Ok-Topk round-2 tail (round2_tail.hip): global selection over the gathered
+// survivors + residual credit.  tau is None on a threshold iteration (k not
+// given) and when nothing was gathered.
+// ---------------------------------------------------------------------------
+static void check_round2_common(const torch::Tensor& residual,
+                                const torch::Tensor& idx,
+                                const c10::optional<int64_t>& k) {
+    check_f32_1d(residual, "residual");
+    check_i32_1d(idx, "idx");
+    TORCH_CHECK(idx.device() == residual.device(), "idx must be on residual's device");
+    TORCH_CHECK(idx.numel() <= INT32_MAX, "round2_tail: idx too long");
+    TORCH_CHECK(!k.has_value() || k.value() >= 1, "k must be >= 1");
+}
+
+// exact iteration over (all_idx, all_val): the select of topk_select over
+// all_val, written through launch_r2_write.  `hist` holds level 1 already
+// when the wire decode counted it.
+static std::tuple<torch::Tensor, torch::Tensor, py::object> round2_exact(
+    torch::Tensor& residual, torch::Tensor& idx, torch::Tensor& all_idx,
+    torch::Tensor& all_val, int64_t k, torch::Tensor hist, bool level1_done) {
+    const int64_t S = all_idx.numel();
+    const int64_t kout = k < S ? k : S;
+    auto g_idx = torch::empty({kout}, all_idx.options());
+    auto g_val = torch::empty({kout}, all_val.options());
+    R2Write r2{all_idx.data_ptr<int32_t>(), idx.data_ptr<int32_t>(),
+               (int)idx.numel(), residual.data_ptr<float>(), residual.numel()};
+    auto state = tk_select_run(all_val.data_ptr<float>(), S, kout, false,
+                               nullptr, nullptr, nullptr, hist, level1_done,
+                               g_idx, g_val, &r2);
+    return std::make_tuple(g_idx, g_val, py::cast(tk_state_tau(state)));
+}
+
+static std::tuple<torch::Tensor, torch::Tensor, py::object> round2_tail_(
+    torch::Tensor residual, torch::Tensor idx, torch::Tensor all_idx,
+    torch::Tensor all_val, c10::optional<int64_t> k) {
+    check_round2_common(residual, idx, k);
+    check_i32_1d(all_idx, "all_idx");
+    check_f32_1d(all_val, "all_val");
+    TORCH_CHECK(all_idx.numel() == all_val.numel(), "all_idx / all_val length mismatch");
+    TORCH_CHECK(all_idx.device() == residual.device() &&
+                    all_val.device() == residual.device(),
+                "round2_tail_: device mismatch");
+    const int64_t S = all_idx.numel();
+    TORCH_CHECK(S <= INT32_MAX, "round2_tail_: gathered lists too long");
+    const at::cuda::CUDAGuard guard(residual.device());
+    if (!k.has_value() || S == 0) {
+        // the gathered lists are the selection as they stand
+        if (S > 0 && idx.numel() > 0)
+            launch_r2_credit(all_idx.data_ptr<int32_t>(), (int)S,
+                             idx.data_ptr<int32_t>(), (int)idx.numel(),
+                             residual.data_ptr<float>(), residual.numel(),
+                             cur_stream());
+        return std::make_tuple(all_idx, all_val, py::object(py::none()));
+    }
+    auto hist = torch::zeros({2048}, all_idx.options());
+    return round2_exact(residual, idx, all_idx, all_val, k.value(), hist, false);
+}
+
+static std::tuple<torch::Tensor, torch::Tensor, py::object> round2_tail_wire_(
+    torch::Tensor residual, torch::Tensor idx, torch::Tensor buf,
+    std::vector<int64_t> counts, bool wire_bf16, c10::optional<int64_t> k) {
+    check_round2_common(residual, idx, k);
+    check_i32_1d(buf, "buf");
+    TORCH_CHECK(buf.device() == residual.device(), "buf must be on residual's device");
+    const at::cuda::CUDAGuard guard(residual.device());
+    int64_t S = 0, words = 0;
+    auto meta = wire_tables(counts, wire_bf16, buf, &S, &words);
+    TORCH_CHECK(words <= buf.numel(), "wire codec: buf holds ", buf.numel(),
+                " words, counts need ", words);
+    auto all_idx = torch::empty({S}, buf.options());
+    auto all_val = torch::empty({S}, buf.options().dtype(torch::kFloat32));
+    if (S == 0)
+        return std::make_tuple(all_idx, all_val, py::object(py::none()));
+    const bool exact = k.has_value();
+    torch::Tensor hist;
+    if (exact) hist = torch::zeros({2048}, buf.options());
+    launch_r2_wire_tail(
+        buf.data_ptr<int32_t>(), meta.data_ptr<int>(), (int)counts.size(), (int)S,
+        wire_bf16 ? 1 : 0, all_idx.data_ptr<int32_t>(), all_val.data_ptr<float>(),
+        idx.data_ptr<int32_t>(), (int)idx.numel(), residual.data_ptr<float>(),
+        residual.numel(),
+        exact ? reinterpret_cast<unsigned int*>(hist.data_ptr<int>()) : nullptr,
+        cur_stream());
+    if (!exact)
+        return std::make_tuple(all_idx, all_val, py::object(py::none()));
+    return round2_exact(residual, idx, all_idx, all_val, k.value(), hist, true);
+}
+
 static std::vector<torch::Tensor> linear_gelu(torch::Tensor x, torch::Tensor w,
                                               torch::Tensor bias, bool apply_gelu,
                                               bool want_pre) {
@@ -1527,6 +1644,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "dest[idx - base] += val for every wire entry (fused unpack-reduce)",
           py::arg("dest"), py::arg("buf"), py::arg("counts"), py::arg("base"),
           py::arg("wire_bf16"));
+    m.def("round2_tail_", &round2_tail_,
+          "Ok-Topk round-2 tail over gathered (all_idx, all_val): global "
+          "selection (all entries, or exact top-k ascending) + residual "
+          "credit; returns (g_idx, g_val, tau or None)",
+          py::arg("residual"), py::arg("idx"), py::arg("all_idx"),
+          py::arg("all_val"), py::arg("k") = py::none());
+    m.def("round2_tail_wire_", &round2_tail_wire_,
+          "round2_tail_ over the allgathered wire buffer (decode fused in)",
+          py::arg("residual"), py::arg("idx"), py::arg("buf"), py::arg("counts"),
+          py::arg("wire_bf16"), py::arg("k") = py::none());
     m.def("add_ln_fwd", &add_ln_fwd, "fused y=LN(x+r) forward (bf16)");
     m.def("add_ln_bwd", &add_ln_bwd, "fused add+LN backward (bf16, fp32 col sums)");
     m.def("linear_gelu", &linear_gelu,

@@ -489,6 +489,50 @@ def unpack_scatter_add_(dest: torch.Tensor, buf: torch.Tensor, counts,
     return dest
 
 
+def round2_tail_(residual: torch.Tensor, idx: torch.Tensor,
+                 all_idx: torch.Tensor, all_val: torch.Tensor, k=None):
+    """Ok-Topk round-2 tail over the gathered survivors (all_idx int32
+    ascending and unique, all_val fp32) and this rank's local selection idx
+    (int32 ascending, unique): the global selection plus the residual
+    credit.  Returns (g_idx, g_val, tau).
+
+    k is None (threshold iteration) or no entry was gathered: the selection
+    is every gathered entry, returned as passed in; tau is None.  k given:
+    the min(k, S) entries of largest |all_val| by topk_select's rule (abs
+    bit pattern, the tie class at the k-th magnitude filled from the lowest
+    position), g_idx ascending, tau the k-th magnitude.
+
+    Credit: residual[j] = +0.0 for every j in both g_idx and idx, and no
+    other write; a matched j outside [0, residual.numel()) is dropped.
+
+    Reference: k2globalthreshold + gather and intersect1d +
+    update_residuals, VGG/allreducer.py:833-845,1051-1052."""
+    if k is not None and k < 1:
+        raise ValueError("round2_tail_: k must be >= 1")
+    if all_idx.numel() != all_val.numel():
+        raise ValueError("round2_tail_: all_idx / all_val length mismatch")
+    if k is None or all_idx.numel() == 0:
+        g_idx, g_val, tau = all_idx, all_val, None
+    else:
+        pos, g_val, tau = topk_select(all_val, k)
+        g_idx = all_idx[pos.long()]
+    if idx.numel() and g_idx.numel():
+        hit = g_idx[isin_sorted(g_idx, idx)].long()
+        hit = hit[(hit >= 0) & (hit < residual.numel())]
+        residual.reshape(-1)[hit] = 0.0
+    return g_idx, g_val, tau
+
+
+def round2_tail_wire_(residual: torch.Tensor, idx: torch.Tensor,
+                      buf: torch.Tensor, counts, wire_bf16: bool, k=None):
+    """round2_tail_ with the gathered survivors given as the allgathered
+    wire buffer (`counts` are ELEMENT counts per rank segment): bit-equal to
+    round2_tail_ over unpack_segments(buf, counts, wire_bf16), which with
+    k=None is also the returned pair."""
+    all_idx, all_val = unpack_segments(buf, counts, wire_bf16)
+    return round2_tail_(residual, idx, all_idx, all_val, k)
+
+
 def grad_clip_scale(t: torch.Tensor, max_norm: float) -> torch.Tensor:
     gn = t.reshape(-1).float().norm(p=2)
     scale = torch.where(gn > max_norm, max_norm / (gn + 1e-6),

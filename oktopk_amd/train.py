@@ -49,6 +49,10 @@ def build_argparser() -> argparse.ArgumentParser:
     p.add_argument("--device-wire", action="store_true",
                    help="oktopk device-side wire codec (region pack + fused "
                         "unpack-reduce kernels)")
+    p.add_argument("--device-round2", action="store_true",
+                   help="oktopk device-side round-2 tail (global select + "
+                        "residual credit in one op, ascending on every "
+                        "iteration)")
     p.add_argument("--device-exact-topk", action="store_true",
                    help="topkA/topkA2/gtopk: device-resident exact top-k "
                         "selection and sparse tree merge instead of "
@@ -102,6 +106,7 @@ def main(argv=None) -> int:
                      profiling=args.profiling, profiling_norm=args.profiling_norm,
                      balanced_allgather=args.balanced_allgather,
                      device_wire=args.device_wire,
+                     device_round2=args.device_round2,
                      gaussian_device_select=args.gaussian_device_select,
                      device_exact_topk=args.device_exact_topk,
                      pipeline_chunks=args.pipeline_chunks)

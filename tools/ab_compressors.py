@@ -34,6 +34,12 @@ def main():
     ap.add_argument("--device-exact-topk", action="store_true",
                     help="topkA/topkA2/gtopk select and merge with the exact-k "
                          "HIP ops (EngineConfig.device_exact_topk)")
+    ap.add_argument("--device-round2", action="store_true",
+                    help="oktopk round-2 tail (global select + residual "
+                         "credit) with the HIP op (OkTopkConfig.device_round2)")
+    ap.add_argument("--global-recompute-interval", type=int, default=None,
+                    help="override OkTopkConfig.global_threshold_recompute_"
+                         "interval (1 makes every oktopk step an exact one)")
     args = ap.parse_args()
 
     comm = init_from_env()
@@ -44,7 +50,11 @@ def main():
             continue
         cfg = EngineConfig.preset("bert", compressor=comp, density=args.density,
                                   dense_warmup_iters=0,
-                                  device_exact_topk=args.device_exact_topk)
+                                  device_exact_topk=args.device_exact_topk,
+                                  device_round2=args.device_round2)
+        if args.global_recompute_interval is not None:
+            cfg.oktopk.global_threshold_recompute_interval = \
+                args.global_recompute_interval
         tr = Trainer(args.model, batch_size=args.batch_size, seq_len=128,
                      comm=comm, cfg=cfg,
                      dtype="bf16" if torch.cuda.is_available() else "fp32")
@@ -72,7 +82,10 @@ def main():
     if comm.rank == 0:
         print(f"# {args.model} bs{args.batch_size} density={args.density} "
               f"P={comm.size} steps={args.steps}"
-              + (" device_exact_topk" if args.device_exact_topk else ""))
+              + (" device_exact_topk" if args.device_exact_topk else "")
+              + (" device_round2" if args.device_round2 else "")
+              + (f" global_recompute_interval={args.global_recompute_interval}"
+                 if args.global_recompute_interval is not None else ""))
         print(f"{'compressor':12s} {'ms/step':>9s}  phases(ms)")
         for comp, ms, ph in rows:
             pstr = " ".join(f"{k}={v:.2f}" for k, v in sorted(ph.items()))

@@ -333,6 +333,78 @@ def topk_rows(reps, sizes=(109_500_000, 336_000_000), density=0.001):
         del t0, r0, g16, t, r
 
 
+def round2_rows(reps, sizes=(109_500_000, 336_000_000), density=0.001, P=8):
+    """Ok-Topk round-2 tail (ops/csrc/round2_tail.hip) against the torch
+    composition the engine runs without device_round2, same process, same
+    inputs, arms alternating: ops.unpack_segments, then on an exact
+    iteration abs + torch.topk(sorted=True) + .item() + two gathers, then
+    the residual credit through the persistent n-element bool mask (two
+    int64 index copies, two index_puts, zero_at_masked_) — against one
+    ops.round2_tail_wire_ call on the gathered buffer.  BERT-base and
+    BERT-large flat sizes at density 0.1 %, gathered S = 4k/3 and 4k entries
+    in 8 segments, fp32 and bf16 wire, threshold (k=None) and exact mode;
+    the local selection holds ~k entries, half of them gathered ones.  Each
+    call is timed alone; median and min..max over `reps` repeats."""
+    from oktopk_amd import ops
+
+    print(f"# round-2 tail, density={density}, P={P} segments, "
+          f"{reps} repeats/row")
+    print(f"{'path':58s} {'median ms':>10s} {'min ms':>9s} {'max ms':>9s}")
+    for n in sizes:
+        k = max(1, int(n * density))
+        g = torch.Generator().manual_seed(0)
+        residual = torch.full((n,), 0.5, device="cuda")
+        mask = torch.zeros(n, dtype=torch.bool, device="cuda")
+        print(f"# n={n} k={k}: mask bytes the flag no longer allocates = {n}")
+        for S in (4 * k // 3, 4 * k):
+            pool = torch.randint(0, n, (2 * S + 2 * k,), generator=g).unique()
+            pool = pool[torch.randperm(pool.numel(), generator=g)]
+            all_idx = pool[:S].sort().values.to(torch.int32).cuda()
+            # local selection: k/2 gathered entries + k/2 others
+            idx = torch.cat([pool[:k // 2], pool[S:S + k - k // 2]]) \
+                .sort().values.to(torch.int32).cuda()
+            bounds = torch.tensor([i * (n // P) for i in range(P)] + [n],
+                                  dtype=torch.int64)
+            for wire in ("fp32", "bf16"):
+                bf = wire == "bf16"
+                val = torch.randn(S, generator=g).cuda()
+                buf, counts = ops.pack_regions(all_idx, val, bounds, bf)
+
+                def torch_tail(kk):
+                    a_idx, a_val = ops.unpack_segments(buf, counts, bf)
+                    tau = None
+                    if kk is not None:
+                        top = torch.topk(a_val.abs(), min(kk, a_val.numel()),
+                                         sorted=True)
+                        tau = float(top.values[-1].item())
+                        a_idx, a_val = a_idx[top.indices], a_val[top.indices]
+                    mask[a_idx.long()] = True
+                    ops.zero_at_masked_(residual, idx, mask)
+                    mask[a_idx.long()] = False
+                    return a_idx, a_val, tau
+
+                for mode, kk in (("threshold", None), ("exact", k)):
+                    times, last = _alternate(
+                        (("torch", lambda: torch_tail(kk)),
+                         ("hip", lambda: ops.round2_tail_wire_(
+                             residual, idx, buf, counts, bf, kk))),
+                        lambda: None, reps)
+                    # torch.topk may pick other members of the tie class at
+                    # the k-th magnitude (bf16 values tie): same magnitudes,
+                    # same tau
+                    a, b = (last[x][1].abs().sort().values
+                            for x in ("torch", "hip"))
+                    assert torch.equal(a, b), "selections differ"
+                    assert last["torch"][2] == last["hip"][2]
+                    for arm, label in (("torch", "torch unpack+topk+mask"),
+                                       ("hip", "round2_tail_wire_")):
+                        ts = times[arm]
+                        print(f"{mode:9s} {wire} S={S:<8d} n={n:<10d} "
+                              f"{label:24s} {ts[len(ts) // 2]:10.3f} "
+                              f"{ts[0]:9.3f} {ts[-1]:9.3f}")
+        del residual, mask
+
+
 def sparse_step_rows(iters, density=0.001):
     """The optimizer tail at the 109.5 M flat scale with k = 0.1 %: the dense
     hand-over (zero fill + scatter + dense sum of squares + Adam over p, g,
@@ -398,10 +470,11 @@ def main():
     ap.add_argument("--iters", type=int, default=None,
                     help="calls per timed window (default 20; 1000 for the "
                          "microsecond-scale --only wire rows; repeats per "
-                         "row, default 15, for --only gauss and topk)")
+                         "row, default 15, for --only gauss, topk and "
+                         "round2)")
     ap.add_argument("--only", default="",
                     choices=["", "colsum", "wire", "gauss", "sparse_step",
-                             "topk"],
+                             "topk", "round2"],
                     help="run just one group of rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -419,6 +492,9 @@ def main():
         return
     if args.only == "topk":
         topk_rows(args.iters or 15)
+        return
+    if args.only == "round2":
+        round2_rows(args.iters or 15)
         return
     args.iters = args.iters or 20
     g = torch.Generator().manual_seed(0)
