@@ -11,6 +11,8 @@ Contract shared with the HIP backend (oktopk_amd/ops/csrc):
 """
 from __future__ import annotations
 
+import collections
+import math
 from typing import Tuple
 
 import torch
@@ -39,6 +41,8 @@ __all__ = [
     "unpack_segments",
     "unpack_scatter_add_",
     "colsum_torch_order",
+    "attention_ref64",
+    "attention_bf16_staged",
 ]
 
 
@@ -600,3 +604,226 @@ def colsum_torch_order(x: torch.Tensor, bh: int = 2, ctas: int = 32,
             g = g + P[j]
         G.append(g)
     return tree(G)
+
+
+# -- flash attention --------------------------------------------------------
+# Two references of the op of ops/csrc/attention_fa.hip over the packed bf16
+# projection buffer qkv [b, s, 3*nh*64]: ctx = (softmax(QK^T/8 + mask) *
+# keep) @ V, and its gradient for an upstream gy [b, s, nh*64].  mask is
+# additive over keys ([b, s] or anything that reshapes to it; rounded to
+# bf16 as the binding does) or None; keep is [b*nh, s, s] holding
+# 1/keep_prob where the dropout kept an entry and 0 where it dropped it, or
+# None.  Both return AttnRef(out [b, s, nh*64], lse [b*nh, s],
+# dqkv [b, s, 3*nh*64]) in their working precision.
+
+AttnRef = collections.namedtuple("AttnRef", ["out", "lse", "dqkv"])
+
+ATTN_HD = 64
+
+
+def attn_split_heads(qkv: torch.Tensor, num_heads: int):
+    """q, k, v as [b, nh, s, 64] views of the packed [b, s, 3*nh*64]."""
+    b, s, _ = qkv.shape
+    return qkv.reshape(b, s, 3, num_heads, ATTN_HD).permute(2, 0, 3, 1, 4).unbind(0)
+
+
+def attn_merge_heads(x: torch.Tensor) -> torch.Tensor:
+    """[b, nh, s, 64] -> [b, s, nh*64]."""
+    b, nh, s, hd = x.shape
+    return x.permute(0, 2, 1, 3).reshape(b, s, nh * hd)
+
+
+def _attn_mask_keep(qkv, mask, keep, num_heads, dtype):
+    b, s, _ = qkv.shape
+    m = None
+    if mask is not None and mask.numel():
+        m = mask.reshape(b, 1, 1, s).to(torch.bfloat16).to(dtype)
+    kp = None
+    if keep is not None:
+        kp = keep.reshape(b, num_heads, s, s).to(dtype)
+    return m, kp
+
+
+def _bf16_round(x: torch.Tensor) -> torch.Tensor:
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+def attention_ref64(qkv, mask, gy, num_heads, keep=None) -> AttnRef:
+    """The operation in fp64 from the same bf16 inputs; the gradient is
+    autograd's, in fp64.  This is the oracle."""
+    x = qkv.detach().double().requires_grad_(True)
+    q, k, v = attn_split_heads(x, num_heads)
+    m, kp = _attn_mask_keep(qkv, mask, keep, num_heads, torch.float64)
+    sc = q @ k.transpose(-1, -2) / math.sqrt(ATTN_HD)
+    if m is not None:
+        sc = sc + m
+    lse = torch.logsumexp(sc, dim=-1)
+    p = torch.softmax(sc, dim=-1)
+    if kp is not None:
+        p = p * kp
+    out = attn_merge_heads(p @ v)
+    (dqkv,) = torch.autograd.grad(out, x, gy.detach().double())
+    b, s, _ = qkv.shape
+    return AttnRef(out.detach(), lse.detach().reshape(b * num_heads, s), dqkv)
+
+
+# attention_bf16_staged is built from the steps below so that each can be
+# driven on its own (the CPU tests feed them deliberately wrong arguments).
+# All of them work in fp32 on whole rows (no tiling) over [b, nh, s, *]
+# tensors and round to bf16 exactly where the kernels do.
+
+def attn_staged_inputs(qkv, mask, gy, num_heads, keep=None):
+    """(q, k, v, go [b, nh, s, 64], mask [b, 1, 1, s] | None,
+    keep [b, nh, s, s] | None, scale), all fp32."""
+    b, s, _ = qkv.shape
+    q, k, v = attn_split_heads(qkv.detach().float(), num_heads)
+    m, kp = _attn_mask_keep(qkv, mask, keep, num_heads, torch.float32)
+    go = gy.detach().float().reshape(b, s, num_heads, ATTN_HD).permute(0, 2, 1, 3)
+    return q, k, v, go, m, kp, 1.0 / math.sqrt(ATTN_HD)
+
+
+def attn_staged_result(o, lse, dq, dk, dv) -> AttnRef:
+    b, nh, s, _ = o.shape
+    return AttnRef(attn_merge_heads(o), lse.reshape(b * nh, s),
+                   attn_pack_grads(dq, dk, dv))
+
+
+def attn_staged_scores(q, k, mask, scale):
+    """s = (q.k)*scale + mask, fp32."""
+    sc = (q @ k.transpose(-1, -2)) * scale
+    return sc if mask is None else sc + mask
+
+
+def attn_staged_forward(q, k, v, mask, keep, scale):
+    """attn_fwd_fa_kernel: m = rowmax, e = exp(s - m), l = sum(e) (before
+    dropout, from the unrounded e), P~ = bf16(e*keep), O = bf16((P~ @ V)/l),
+    lse = m + log(l).  Returns (O bf16-rounded, lse, O before rounding)."""
+    sc = attn_staged_scores(q, k, mask, scale)
+    m = sc.amax(dim=-1, keepdim=True)
+    e = torch.exp(sc - m)
+    l = e.sum(dim=-1, keepdim=True)
+    pt = _bf16_round(e if keep is None else e * keep)
+    o32 = (pt @ v) / l
+    return _bf16_round(o32), (m + torch.log(l)).squeeze(-1), o32
+
+
+def attn_staged_p(q, k, lse, mask, scale):
+    """The backward's recomputed P = exp(s - lse), fp32, not rounded."""
+    return torch.exp(attn_staged_scores(q, k, mask, scale) - lse.unsqueeze(-1))
+
+
+def attn_staged_ds(p, go, v, dvec, keep, scale):
+    """dP = (gO @ V^T)*keep, dS = bf16(p*(dP - D)*scale)."""
+    dp = go @ v.transpose(-1, -2)
+    if keep is not None:
+        dp = dp * keep
+    return _bf16_round(p * (dp - dvec.unsqueeze(-1)) * scale)
+
+
+def attn_staged_dq(ds, k):
+    return _bf16_round(ds @ k)
+
+
+def attn_staged_dk(ds, q):
+    return _bf16_round(ds.transpose(-1, -2) @ q)
+
+
+def attn_staged_dv(p, go, keep):
+    a = _bf16_round(p if keep is None else p * keep)
+    return _bf16_round(a.transpose(-1, -2) @ go)
+
+
+def attn_pack_grads(dq, dk, dv) -> torch.Tensor:
+    """[b, nh, s, 64] x 3 -> packed [b, s, 3*nh*64]."""
+    b, nh, s, hd = dq.shape
+    return torch.stack([dq, dk, dv], 0).permute(1, 3, 0, 2, 4).reshape(
+        b, s, 3 * nh * hd)
+
+
+def attention_bf16_staged(qkv, mask, gy, num_heads, keep=None) -> AttnRef:
+    """The same mathematics in fp32 with a bf16 rounding at exactly the
+    points where the kernels of attention_fa.hip round.  NOT an oracle: its
+    distance from attention_ref64 is what the kernels' chosen precision
+    costs when everything else is right — the yardstick the accuracy tests
+    scale their bounds by.  Left out on purpose: __expf/__logf, the MFMA
+    accumulation order and the fp32 reorderings of the online rescale."""
+    q, k, v, go, m, kp, scale = attn_staged_inputs(qkv, mask, gy, num_heads, keep)
+    o, lse, _ = attn_staged_forward(q, k, v, m, kp, scale)
+    dvec = (go * o).sum(dim=-1)  # attn_rowdot, from the bf16 O
+    p = attn_staged_p(q, k, lse, m, scale)
+    ds = attn_staged_ds(p, go, v, dvec, kp, scale)
+    return attn_staged_result(o, lse, attn_staged_dq(ds, k),
+                              attn_staged_dk(ds, q), attn_staged_dv(p, go, kp))
+
+
+# Accuracy metrics of the attention tests.  Each tensor is viewed as rows of
+# 64 (one head's vector at one position); both metrics are relative to the
+# fp64 reference.
+
+def attn_tensors(res: AttnRef, num_heads: int) -> dict:
+    """out, dq, dk, dv as [rows, 64] fp64, rows indexed (b, position, head)."""
+    b, s, _ = res.out.shape
+    g = res.dqkv.reshape(b, s, 3, num_heads, ATTN_HD).double()
+    return {"out": res.out.double().reshape(-1, ATTN_HD),
+            "dq": g[:, :, 0].reshape(-1, ATTN_HD),
+            "dk": g[:, :, 1].reshape(-1, ATTN_HD),
+            "dv": g[:, :, 2].reshape(-1, ATTN_HD)}
+
+
+def attn_rel_fro(x: torch.Tensor, ref: torch.Tensor) -> float:
+    """||x - ref||_F / ||ref||_F."""
+    return float((x - ref).norm() / ref.norm())
+
+
+def attn_row_max(x: torch.Tensor, ref: torch.Tensor) -> float:
+    """max over rows ||x_row - ref_row||_2 / median over rows ||ref_row||_2,
+    so that one wrong row is not diluted by the rest of the tensor.  Where
+    more than half of the reference rows are exactly zero (dK and dV rows of
+    keys whose mask underflows the softmax) the median is taken over the
+    nonzero rows: the denominator only sets the unit, and cancels whenever
+    two results are compared against the same reference."""
+    norms = ref.norm(dim=1)
+    med = norms.median()
+    if float(med) == 0.0:
+        med = norms[norms > 0].median()
+    return float((x - ref).norm(dim=1).max() / med)
+
+
+# A kernel result passes when each metric, per tensor, is at most this many
+# times the same metric of attention_bf16_staged on the same inputs.  The
+# staged reference carries every bf16 rounding the kernels make; the factor
+# covers what it leaves out on purpose — __expf/__logf, the MFMA
+# accumulation order and the fp32 reorderings of the online rescale.  The
+# staged reference sits at rel_fro 0.0023-0.0036, while the smallest error
+# worth catching, 2 % in `scale` on the dS path, lifts dQ/dK to 0.020 (8.5x
+# the floor) and one duplicated dQ row gives row_max >= 1: 3x leaves room
+# for the kernel and still catches both.  If a case exceeds it the kernel
+# is wrong or rounds where the emulation does not; the factor is not tuned.
+ATTN_STAGED_FACTOR = 3.0
+
+
+def attn_metrics(res: AttnRef, ref64: AttnRef, num_heads: int) -> dict:
+    """{tensor: (rel_fro, row_max)} of res against the fp64 reference."""
+    x, r = attn_tensors(res, num_heads), attn_tensors(ref64, num_heads)
+    return {n: (attn_rel_fro(x[n], r[n]), attn_row_max(x[n], r[n])) for n in r}
+
+
+def attn_over_staged(metrics: dict, staged: dict, names=None) -> list:
+    """The (tensor, metric) pairs of `metrics` that exceed
+    ATTN_STAGED_FACTOR times the staged reference's."""
+    bad = []
+    for n in (names or metrics):
+        for i, what in enumerate(("rel_fro", "row_max")):
+            if not metrics[n][i] <= ATTN_STAGED_FACTOR * staged[n][i]:
+                bad.append((n, what))
+    return bad
+
+
+def attn_lse_bound(lse64: torch.Tensor) -> torch.Tensor:
+    """Elementwise bound on |lse - lse64|: max(2^-10, 2*ulp_fp32(|lse64|)).
+    2^-10 keeps the relative error an LSE error induces in every recomputed
+    P below half a bf16 ulp, the precision P is staged at; the ulp term
+    only matters where |lse| ~ 1e4 (a fully masked batch)."""
+    a = lse64.abs().float()
+    ulp = (torch.nextafter(a, torch.full_like(a, float("inf"))) - a).double()
+    return torch.clamp(2.0 * ulp, min=2.0 ** -10)
