@@ -17,7 +17,7 @@ from .allreducer import AllReducer, COMPRESSORS  # noqa: F401
 def __getattr__(name):
     # Lazy top-level exports for the heavier user-facing classes (keeps
     # `import oktopk_amd` light for kernels-only use; no circular imports).
-    if name in ("DistributedOptimizer", "FlatBertAdam"):
+    if name in ("DistributedOptimizer", "FlatBertAdam", "FlatSGD"):
         from . import optimizer
 
         return getattr(optimizer, name)

@@ -129,6 +129,13 @@ class AllReducer:
         # sparse hand-over (run(..., sparse_ok=True)): the last run's result
         # as a SparseGrad, or None when that run densified as usual
         self.sparse_result: Optional[SparseGrad] = None
+        # the same hand-over per tensor name, for callers that run several
+        # named tensors per step (the bucketed optimizers, partly on the
+        # reducer thread): every run(name, ...) overwrites its entry, with
+        # None when that run densified.  run_many's pipelined path always
+        # densifies (a sparse hand-over from _oktopk_pipeline does not
+        # exist) and sets its items' entries to None.
+        self.sparse_results: Dict[str, Optional[SparseGrad]] = {}
         self._sparse_ok = False
 
     def set_comm(self, comm: Comm) -> None:
@@ -175,6 +182,7 @@ class AllReducer:
             torch.cuda.synchronize()
         comp = self.cfg.compressor
         self.sparse_result = None
+        self.sparse_results[name] = None
         # profiling_norm compares the dense result against the oracle
         self._sparse_ok = bool(sparse_ok) and not self.cfg.profiling_norm
         if comp == "oktopk" and self.cfg.oktopk.pipeline_chunks > 1:
@@ -263,6 +271,7 @@ class AllReducer:
                         {k: round(v, 4) for k, v in self.timers.get(name, {}).items()})
 
         st.counter += 1
+        self.sparse_results[name] = self.sparse_result
         return tensor
 
     # -- dense ----------------------------------------------------------
@@ -668,6 +677,7 @@ class AllReducer:
             torch.cuda.synchronize()
         parts, warm = [], []
         for name, tensor, g in items:
+            self.sparse_results[name] = None  # the pipeline densifies
             t = tensor.reshape(-1)
             st = self.state(name, t)
             it = st.counter

@@ -243,11 +243,16 @@ def scatter_gt_credit_(result, residual, idx, val, tau, scale=1.0) -> int:
 # or zero + scatter_gt_credit_, would have written.
 
 def sparse_sumsq_into_(acc: torch.Tensor, idx, val, scale: float,
-                       tau: float) -> None:
+                       tau: float, n=None) -> None:
     """acc (fp64[1], same device) += sum of squares of the dense gradient a
-    sparse one stands for; no host sync on GPU."""
-    return _backend(val).sparse_sumsq_into_(acc, idx, val, float(scale),
-                                            float(tau))
+    sparse one stands for; no host sync on GPU.  With `n` (the dense length)
+    the CPU reference densifies and sums in the dense route's order, as
+    grad_clip_scale_sparse does; the HIP op ignores it."""
+    b = _backend(val)
+    if b is _ref and n is not None:
+        return b.sumsq_into_(acc, b.densify_sparse_grad(
+            idx, val, 0, int(n), float(scale), float(tau)))
+    return b.sparse_sumsq_into_(acc, idx, val, float(scale), float(tau))
 
 
 def grad_clip_scale_sparse(idx, val, scale: float, tau: float,
@@ -288,6 +293,39 @@ def fused_adam_sparse_mirror_(param, idx, val, base, scale, tau, exp_avg,
                          exp_avg, exp_avg_sq, float(lr), float(beta1),
                          float(beta2), float(eps), float(weight_decay), gscale)
     param_bf16.copy_(param)
+
+
+# -- flat SGD ------------------------------------------------------------------
+
+def sgd_step_(param, grad, momentum_buf, lr, momentum, weight_decay, nesterov,
+              gscale=None):
+    """SGD step (momentum / nesterov / weight decay, no dampening) over flat
+    fp32 tensors, every multiply and add rounded separately (the contract is
+    in ops/reference.py).  `gscale` (optional 1-elem tensor) pre-scales the
+    gradient read — the device-resident grad clip.  `momentum_buf` is not
+    touched when momentum == 0 and may then be empty."""
+    return _backend(param).sgd_step_(
+        param, grad, momentum_buf, float(lr), float(momentum),
+        float(weight_decay), bool(nesterov), gscale)
+
+
+def sgd_step_sparse_(param, idx, val, base, scale, tau, momentum_buf, lr,
+                     momentum, weight_decay, nesterov, gscale=None):
+    """sgd_step_ on the slice [base, base+len(param)) of a sparse gradient:
+    bit-identical to fill_sparse_scaled_ + sgd_step_, without the zero fill,
+    the scatter and the dense gradient read.  Entries outside the slice are
+    ignored."""
+    return _backend(param).sgd_step_sparse_(
+        param, idx, val, int(base), float(scale), float(tau), momentum_buf,
+        float(lr), float(momentum), float(weight_decay), bool(nesterov),
+        gscale)
+
+
+def clip_scale_from_sumsq(acc: torch.Tensor, max_norm: float) -> torch.Tensor:
+    """grad_clip_scale's factor from an fp64[1] sum of squares accumulated
+    with sumsq_into_ / sparse_sumsq_into_ (one accumulator may span several
+    buffers); a 1-elem fp32 tensor on acc's device, no host sync."""
+    return _backend(acc).clip_scale_from_sumsq(acc, float(max_norm))
 
 
 # -- sparse wire codec ([idx int32 | val bits] per segment, fp32 or bf16) ---

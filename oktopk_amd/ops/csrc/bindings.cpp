@@ -51,6 +51,11 @@ void launch_adam_sparse(float*, float*, float*, void*, const float*, int64_t,
                         const int32_t*, const float*, int64_t, int32_t*, int64_t,
                         float, float, float, float, float, float, float,
                         hipStream_t);
+void launch_sgd_step(float*, const float*, float*, const float*, int64_t, float,
+                     float, float, int, hipStream_t);
+void launch_sgd_step_sparse(float*, float*, const float*, int64_t, const int32_t*,
+                            const float*, int64_t, int32_t*, int64_t, float,
+                            float, float, float, float, int, hipStream_t);
 void launch_colsum_into_bf16(const void*, int64_t, int64_t, void*, int,
                              hipStream_t);
 int launch_colsum_exact_bf16(const void*, int64_t, int64_t, void*, int, int,
@@ -849,6 +854,66 @@ static void fused_adam_sparse_mirror_(torch::Tensor p, torch::Tensor idx,
                      b1, b2, eps, wd, gscale);
 }
 
+// -- flat SGD (kernels.hip, "flat SGD") --------------------------------------
+
+static float* sgd_buf_ptr(const torch::Tensor& p, const torch::Tensor& buf,
+                          double momentum) {
+    // buf is untouched without momentum and may then be empty
+    if (momentum == 0.0) return nullptr;
+    check_f32_1d(buf, "buf");
+    TORCH_CHECK(buf.numel() == p.numel() && buf.device() == p.device(),
+                "buf must have p's length and device");
+    return buf.data_ptr<float>();
+}
+
+static void sgd_step_(torch::Tensor p, torch::Tensor g, torch::Tensor buf,
+                      double lr, double momentum, double wd, bool nesterov,
+                      c10::optional<torch::Tensor> gscale) {
+    check_f32_1d(p, "p");
+    check_f32_1d(g, "g");
+    TORCH_CHECK(g.numel() == p.numel() && g.device() == p.device(),
+                "g must have p's length and device");
+    float* bp = sgd_buf_ptr(p, buf, momentum);
+    const at::cuda::CUDAGuard guard(p.device());
+    launch_sgd_step(p.data_ptr<float>(), g.data_ptr<float>(), bp,
+                    gscale_ptr(gscale), p.numel(), (float)lr, (float)momentum,
+                    (float)wd, nesterov ? 1 : 0, cur_stream());
+}
+
+static void sgd_step_sparse_(torch::Tensor p, torch::Tensor idx,
+                             torch::Tensor val, int64_t base, double scale,
+                             double tau, torch::Tensor buf, double lr,
+                             double momentum, double wd, bool nesterov,
+                             c10::optional<torch::Tensor> gscale) {
+    check_f32_1d(p, "p");
+    check_sparse_grad(idx, val);
+    TORCH_CHECK(idx.device() == p.device() && val.device() == p.device(),
+                "idx / val must be on p's device");
+    TORCH_CHECK(base >= 0, "base must be >= 0");
+    float* bp = sgd_buf_ptr(p, buf, momentum);
+    const at::cuda::CUDAGuard guard(p.device());
+    auto tile_start = torch::empty({adam_sparse_ntiles(p.numel()) + 1},
+                                   idx.options());
+    launch_sgd_step_sparse(p.data_ptr<float>(), bp, gscale_ptr(gscale),
+                           p.numel(), idx.data_ptr<int32_t>(),
+                           val.data_ptr<float>(), idx.numel(),
+                           tile_start.data_ptr<int32_t>(), base, (float)scale,
+                           (float)tau, (float)lr, (float)momentum, (float)wd,
+                           nesterov ? 1 : 0, cur_stream());
+}
+
+static torch::Tensor clip_scale_from_sumsq(torch::Tensor acc, double max_norm) {
+    // the clip factor of grad_clip_scale from an already accumulated fp64
+    // sum of squares (sumsq_into_ / sparse_sumsq_into_); no host sync
+    TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == torch::kFloat64 &&
+                acc.numel() == 1, "acc must be a 1-elem cuda fp64 tensor");
+    const at::cuda::CUDAGuard guard(acc.device());
+    auto out = torch::empty({1}, acc.options().dtype(torch::kFloat32));
+    launch_clip_scale(acc.data_ptr<double>(), (float)max_norm,
+                      out.data_ptr<float>(), cur_stream());
+    return out;
+}
+
 static void colsum_bf16_into(torch::Tensor gy, torch::Tensor dst,
                              bool accumulate) {
     // bias gradient: dst[C] (=|+=) sum over all leading dims of a bf16
@@ -1590,6 +1655,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("scale"), py::arg("tau"), py::arg("m"), py::arg("v"),
           py::arg("p_bf16"), py::arg("lr"), py::arg("b1"), py::arg("b2"),
           py::arg("eps"), py::arg("wd"), py::arg("gscale") = py::none());
+    m.def("sgd_step_", &sgd_step_,
+          "flat SGD step (momentum / nesterov / weight decay), unfused "
+          "roundings; buf untouched when momentum == 0",
+          py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("lr"),
+          py::arg("momentum"), py::arg("wd"), py::arg("nesterov"),
+          py::arg("gscale") = py::none());
+    m.def("sgd_step_sparse_", &sgd_step_sparse_,
+          "sgd_step_, gradient given as (idx, val, base, scale, tau)",
+          py::arg("p"), py::arg("idx"), py::arg("val"), py::arg("base"),
+          py::arg("scale"), py::arg("tau"), py::arg("buf"), py::arg("lr"),
+          py::arg("momentum"), py::arg("wd"), py::arg("nesterov"),
+          py::arg("gscale") = py::none());
+    m.def("clip_scale_from_sumsq", &clip_scale_from_sumsq,
+          "clip factor min(1, max/(sqrt(acc)+1e-6)) from an fp64 sum of squares");
     m.def("l2norm", &l2norm, "L2 norm (fp64 accumulate)");
     m.def("colsum_bf16_into", &colsum_bf16_into,
           "bias grad: dst (=|+=) column sum of bf16 [R, C], one launch",

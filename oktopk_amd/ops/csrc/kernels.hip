@@ -1104,6 +1104,199 @@ extern "C" void launch_adam_sparse(float* p, float* m, float* v, void* p_bf16,
                        eps, wd);
 }
 
+// ---------------------------------------------------------------------------
+// flat SGD: momentum / nesterov / weight decay over a flat fp32 slice, dense
+// (sgd_step_kernel) or with the gradient in the sparse form above
+// (sgd_step_sparse_kernel).
+//
+// Arithmetic contract: every multiply and add below is rounded on its own
+// (contraction off, no fma), in this order —
+//   gi = g*gs;  d = gi + wd*p (skipped when wd == 0);
+//   b = buf*mom + d, buf = b;  d = nesterov ? d + mom*b : b;  p = p - lr*d
+// — so the float4 loop, the scalar tail and the sparse kernel are bit-equal
+// by construction, and so is a torch composition of separate mul / add calls
+// (ops/reference.py sgd_step_).  g*gs with gs == 1 is the identity.
+// ---------------------------------------------------------------------------
+#define SGD_WD 1
+#define SGD_MOM 2
+#define SGD_NESTEROV 4
+
+__device__ __forceinline__ float sgd_one(float pi, float gi, float& bi, float lr,
+                                         float mom, float wd, int flags) {
+#pragma clang fp contract(off)
+    float d = gi;
+    if (flags & SGD_WD) {
+        const float w = wd * pi;
+        d = gi + w;
+    }
+    if (flags & SGD_MOM) {
+        const float mb = bi * mom;
+        const float b = mb + d;
+        bi = b;
+        if (flags & SGD_NESTEROV) {
+            const float nb = mom * b;
+            d = d + nb;
+        } else {
+            d = b;
+        }
+    }
+    const float s = lr * d;
+    return pi - s;
+}
+
+// buf is neither read nor written without SGD_MOM (it may be null)
+__global__ void sgd_step_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                float* __restrict__ buf,
+                                const float* __restrict__ gscale_ptr,
+                                int64_t n, int64_t n4, float lr, float mom,
+                                float wd, int flags) {
+#pragma clang fp contract(off)
+    const float gs = gscale_ptr ? *gscale_ptr : 1.f;
+    const bool use_mom = flags & SGD_MOM;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* b4 = reinterpret_cast<float4*>(buf);
+    int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * BLOCK;
+    for (; i < n4; i += stride) {
+        float4 pi = p4[i], gi = g4[i];
+        float4 bi = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (use_mom) bi = b4[i];
+        pi.x = sgd_one(pi.x, gi.x * gs, bi.x, lr, mom, wd, flags);
+        pi.y = sgd_one(pi.y, gi.y * gs, bi.y, lr, mom, wd, flags);
+        pi.z = sgd_one(pi.z, gi.z * gs, bi.z, lr, mom, wd, flags);
+        pi.w = sgd_one(pi.w, gi.w * gs, bi.w, lr, mom, wd, flags);
+        if (use_mom) b4[i] = bi;
+        p4[i] = pi;
+    }
+    for (i = n4 * 4 + (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
+         i += stride) {
+        float bi = 0.f;
+        if (use_mom) bi = buf[i];
+        const float pn = sgd_one(p[i], g[i] * gs, bi, lr, mom, wd, flags);
+        if (use_mom) buf[i] = bi;
+        p[i] = pn;
+    }
+}
+
+static inline int sgd_flags(float mom, float wd, int nesterov) {
+    return (wd != 0.f ? SGD_WD : 0) | (mom != 0.f ? SGD_MOM : 0) |
+           (nesterov ? SGD_NESTEROV : 0);
+}
+
+extern "C" void launch_sgd_step(float* p, const float* g, float* buf,
+                                const float* gscale, int64_t n, float lr,
+                                float mom, float wd, int nesterov,
+                                hipStream_t stream) {
+    if (n <= 0) return;
+    const int flags = sgd_flags(mom, wd, nesterov);
+    if (!(flags & SGD_MOM)) buf = nullptr;
+    bool aligned = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0;
+    int64_t n4 = aligned ? n >> 2 : 0;
+    hipLaunchKernelGGL(sgd_step_kernel, dim3(n_blocks(n, 8)), dim3(BLOCK), 0,
+                       stream, p, g, buf, gscale, n, n4, lr, mom, wd, flags);
+}
+
+// sgd_step_kernel with the gradient taken from the sparse form, structured
+// as adam_sparse_kernel: same float4 / scalar-tail split, tile T = the 256
+// float4 a block covers in one iteration, its [start, end) fetched one
+// iteration ahead, a block-uniform hit loop in which each lane patches the
+// component it owns.  An element without a kept hit feeds +0.0f through
+// sgd_one, so every bit matches fill_sparse_scaled_ + sgd_step_kernel.  No
+// LDS, no barrier, no atomics; every store is at an element index < n.
+__global__ void sgd_step_sparse_kernel(float* __restrict__ p,
+                                       float* __restrict__ buf,
+                                       const float* __restrict__ gscale_ptr,
+                                       int64_t n, int64_t n4,
+                                       const int32_t* __restrict__ idx,
+                                       const float* __restrict__ val,
+                                       const int32_t* __restrict__ tile_start,
+                                       int64_t base, float scale,
+                                       uint32_t tau_bits, float lr, float mom,
+                                       float wd, int flags) {
+#pragma clang fp contract(off)
+    const float gs = gscale_ptr ? *gscale_ptr : 1.f;
+    const bool use_mom = flags & SGD_MOM;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* b4 = reinterpret_cast<float4*>(buf);
+    const int64_t nt4 = (n4 + BLOCK - 1) / BLOCK;
+    int64_t T = blockIdx.x;
+    int hs = 0, he = 0;
+    if (T < nt4) { hs = tile_start[T]; he = tile_start[T + 1]; }
+    for (; T < nt4; T += gridDim.x) {
+        const int64_t Tn = T + gridDim.x;
+        int hs_n = 0, he_n = 0;
+        if (Tn < nt4) { hs_n = tile_start[Tn]; he_n = tile_start[Tn + 1]; }
+        const int64_t i = T * BLOCK + threadIdx.x;
+        if (i < n4) {
+            float4 pi = p4[i];
+            float4 bi = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (use_mom) bi = b4[i];
+            float4 gi = make_float4(0.f, 0.f, 0.f, 0.f);
+            const int64_t e0 = base + 4 * i;
+            for (int h = hs; h < he; ++h) {
+                const float x = val[h];
+                const int64_t j = (int64_t)idx[h] - e0;
+                const bool keep = sel_gt(abs_bits(x), tau_bits);
+                const float gv = x * scale;
+                gi.x = (keep & (j == 0)) ? gv : gi.x;
+                gi.y = (keep & (j == 1)) ? gv : gi.y;
+                gi.z = (keep & (j == 2)) ? gv : gi.z;
+                gi.w = (keep & (j == 3)) ? gv : gi.w;
+            }
+            pi.x = sgd_one(pi.x, gi.x * gs, bi.x, lr, mom, wd, flags);
+            pi.y = sgd_one(pi.y, gi.y * gs, bi.y, lr, mom, wd, flags);
+            pi.z = sgd_one(pi.z, gi.z * gs, bi.z, lr, mom, wd, flags);
+            pi.w = sgd_one(pi.w, gi.w * gs, bi.w, lr, mom, wd, flags);
+            if (use_mom) b4[i] = bi;
+            p4[i] = pi;
+        }
+        hs = hs_n; he = he_n;
+    }
+    // scalar tail (n % 4) and the unaligned-base fallback (n4 == 0): each
+    // element looks its own tile up — never the hot path
+    const int64_t stride = (int64_t)gridDim.x * BLOCK;
+    for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n;
+         i += stride) {
+        const int64_t Ts = i / ADAM_TILE;
+        const int ts = tile_start[Ts], te = tile_start[Ts + 1];
+        const int64_t e0 = base + i;
+        float gi = 0.f;
+        for (int h = ts; h < te; ++h) {
+            const float x = val[h];
+            if ((int64_t)idx[h] == e0 && sel_gt(abs_bits(x), tau_bits))
+                gi = x * scale;
+        }
+        float bi = 0.f;
+        if (use_mom) bi = buf[i];
+        const float pn = sgd_one(p[i], gi * gs, bi, lr, mom, wd, flags);
+        if (use_mom) buf[i] = bi;
+        p[i] = pn;
+    }
+}
+
+// tile_start: int32 workspace of adam_sparse_ntiles(n) + 1 entries
+extern "C" void launch_sgd_step_sparse(float* p, float* buf, const float* gscale,
+                                       int64_t n, const int32_t* idx,
+                                       const float* val, int64_t m_entries,
+                                       int32_t* tile_start, int64_t base,
+                                       float scale, float tau, float lr,
+                                       float mom, float wd, int nesterov,
+                                       hipStream_t stream) {
+    if (n <= 0) return;
+    const int flags = sgd_flags(mom, wd, nesterov);
+    if (!(flags & SGD_MOM)) buf = nullptr;
+    int64_t ntiles = adam_sparse_ntiles(n);
+    hipLaunchKernelGGL(sparse_tile_start_kernel, dim3(n_blocks(ntiles + 1)),
+                       dim3(BLOCK), 0, stream, idx, m_entries, base, n, ntiles,
+                       tile_start);
+    bool aligned = (((uintptr_t)p | (uintptr_t)buf) & 15) == 0;
+    int64_t n4 = aligned ? n >> 2 : 0;
+    hipLaunchKernelGGL(sgd_step_sparse_kernel, dim3(n_blocks(n, 8)), dim3(BLOCK),
+                       0, stream, p, buf, gscale, n, n4, idx, val, tile_start,
+                       base, scale, tau_to_bits(tau), lr, mom, wd, flags);
+}
+
 __device__ __forceinline__ float ks_b2f(short u) {
     union { float f; uint32_t i; } c;
     c.i = ((uint32_t)(uint16_t)u) << 16;

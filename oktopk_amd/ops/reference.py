@@ -425,6 +425,59 @@ def fused_adam_sparse_(param, idx, val, base, scale, tau, exp_avg, exp_avg_sq,
                 weight_decay, gscale)
 
 
+# -- flat SGD -----------------------------------------------------------------
+
+def sgd_step_(param, grad, momentum_buf, lr, momentum, weight_decay, nesterov,
+              gscale=None) -> None:
+    """SGD step with momentum / nesterov / weight decay (no dampening), every
+    multiply and add a separate fp32 rounding, in the HIP kernel's order:
+
+        gi = g*gs            (only when gscale is given)
+        d  = gi + wd*p       (skipped when wd == 0)
+        b  = buf*mom + d;  buf = b
+        d  = nesterov ? d + mom*b : b
+        p  = p - lr*d
+
+    Separate mul / add calls and no `alpha=` (which may fuse), so the result
+    has the same bits on any device for finite, non-subnormal data.
+    `momentum_buf` is not touched when momentum == 0."""
+    def f32(x):  # the kernel's scalar arguments are fp32
+        return float(torch.tensor(float(x), dtype=torch.float32))
+
+    lr, momentum, weight_decay = f32(lr), f32(momentum), f32(weight_decay)
+    d = grad
+    if gscale is not None:
+        d = d * gscale.to(grad.device, grad.dtype)
+    if weight_decay != 0:
+        d = d + param * weight_decay
+    if momentum != 0:
+        momentum_buf.mul_(momentum)
+        momentum_buf.add_(d)
+        d = d + momentum_buf * momentum if nesterov else momentum_buf
+    param.sub_(d * lr)
+
+
+def sgd_step_sparse_(param, idx, val, base, scale, tau, momentum_buf, lr,
+                     momentum, weight_decay, nesterov, gscale=None) -> None:
+    """sgd_step_ with the gradient slice [base, base+len(param)) given in
+    sparse form: densify into a temporary, then the dense update."""
+    g = densify_sparse_grad(idx, val, base, param.numel(), scale, tau)
+    sgd_step_(param, g, momentum_buf, lr, momentum, weight_decay, nesterov,
+              gscale)
+
+
+def clip_scale_from_sumsq(acc: torch.Tensor, max_norm: float) -> torch.Tensor:
+    """The clip factor from an fp64 sum of squares, as the HIP clip-scale
+    kernel computes it: gn = sqrt(acc); gn > max ? fp32(max / (gn + 1e-6))
+    : 1, with max rounded to fp32 first.  A 1-elem fp32 tensor."""
+    gn = acc.reshape(1).sqrt()
+    mx = torch.full_like(gn, float(torch.tensor(float(max_norm),
+                                                dtype=torch.float32)))
+    # tensor / tensor: a true division (scalar / tensor is reciprocal * scalar)
+    return torch.where(gn > mx, mx / (gn + 1e-6),
+                       torch.ones_like(gn)).to(torch.float32)
+
+
 # -- sparse wire codec ------------------------------------------------------
 # Wire layout (AllReducer._pack / _unpack / _pack_ints): segment j with c_j
 # elements is c_j int32 indices followed by the values — c_j fp32 words, or

@@ -1,6 +1,6 @@
 """Distributed optimizers over the sparse allreduce engine.
 
-Two surfaces, mirroring the reference:
+Three surfaces, the first two mirroring the reference:
 
 * DistributedOptimizer — Horovod-style wrapper (factory parity with
   /root/reference/VGG/distributed_optimizer.py:203): autograd hooks capture
@@ -15,6 +15,10 @@ Two surfaces, mirroring the reference:
 * FlatBertAdam — BertAdam parity (/root/reference/BERT/bert/transformers/
   optimization.py:68-227): one flat gradient vector for the whole model,
   one engine.run() per step, warmup-scheduled lr, fused Adam step kernels.
+
+* FlatSGD — the DistributedOptimizer machinery with the SGD step itself on
+  flat per-bucket storage: one fused launch per bucket, taking the bucket's
+  gradient in sparse form where the engine hands it over that way.
 """
 from __future__ import annotations
 
@@ -31,7 +35,7 @@ from .allreducer import AllReducer
 from .comm import Comm
 from .config import EngineConfig
 
-__all__ = ["DistributedOptimizer", "FlatBertAdam", "SCHEDULES"]
+__all__ = ["DistributedOptimizer", "FlatBertAdam", "FlatSGD", "SCHEDULES"]
 
 
 # -- BertAdam warmup schedules (reference optimization.py:40-58) -----------
@@ -137,8 +141,11 @@ class _ReducerWorker:
                     if isinstance(item, list):
                         self._reducer.run_many(item)
                     else:
-                        name, flat, grad = item
-                        self._reducer.run(name, flat, grad_src=grad)
+                        # (name, flat, grad_src[, sparse_ok]); the keyword
+                        # is passed only where a bucket asks for it
+                        name, flat, grad = item[:3]
+                        kw = {"sparse_ok": True} if item[3:] == (True,) else {}
+                        self._reducer.run(name, flat, grad_src=grad, **kw)
             except BaseException as e:  # noqa: BLE001 — repropagated in drain()
                 self._exc = e
             finally:
@@ -171,6 +178,11 @@ class _ReducerWorker:
 
 
 class _DistributedOptimizer:
+    # whether completed buckets ask the engine for the sparse hand-over
+    # (AllReducer.run sparse_ok); only a step() that consumes
+    # reducer.sparse_results may turn it on (FlatSGD)
+    _sparse_ok = False
+
     def __init__(
         self,
         optimizer: torch.optim.Optimizer,
@@ -256,12 +268,23 @@ class _DistributedOptimizer:
                     # hand the completed bucket to the reducer thread and
                     # return immediately — backward keeps running while the
                     # engine's collectives and host syncs proceed there
-                    self._worker.submit((b.name, b.flat, None))
+                    self._worker.submit(self._item(b, self._sparse_ok))
                 else:
-                    self.reducer.run(b.name, b.flat)
+                    self._run_bucket(b, self._sparse_ok)
                 b.ready = True
 
         return hook
+
+    @staticmethod
+    def _item(b, sparse_ok: bool):
+        """Work item for the reducer thread."""
+        return (b.name, b.flat, None, True) if sparse_ok else (b.name, b.flat, None)
+
+    def _run_bucket(self, b, sparse_ok: bool) -> None:
+        if sparse_ok:
+            self.reducer.run(b.name, b.flat, sparse_ok=True)
+        else:
+            self.reducer.run(b.name, b.flat)
 
     # reference API surface (VGG/distributed_optimizer.py:185-201) ------
     def stop(self) -> None:
@@ -319,18 +342,24 @@ class _DistributedOptimizer:
             self._apply_mc(b)
             b.ready = True
         whole_step = len(leftovers) == len(self.buckets) and len(leftovers) > 1
+        sparse_ok = self._sparse_ok
+        if whole_step and sparse_ok and self.comm.size == 1:
+            # run_many's pipeline always densifies, and at world 1 there is
+            # no communication for it to overlap: reduce serially and keep
+            # the sparse hand-over
+            whole_step = False
         if self._worker is not None:
             if whole_step:
                 self._worker.submit([(b.name, b.flat, None) for b in leftovers])
             else:
                 for b in leftovers:
-                    self._worker.submit((b.name, b.flat, None))
+                    self._worker.submit(self._item(b, sparse_ok))
             self._worker.drain()
         elif whole_step:
             self.reducer.run_many([(b.name, b.flat, None) for b in leftovers])
         else:
             for b in leftovers:
-                self.reducer.run(b.name, b.flat)
+                self._run_bucket(b, sparse_ok)
 
     def step(self, closure=None):
         if not self.local:
@@ -363,6 +392,9 @@ class _DistributedOptimizer:
 
     def load_state_dict(self, d):
         self.optimizer.load_state_dict(d["optimizer"])
+        self._load_reducer_states(d)
+
+    def _load_reducer_states(self, d):
         for name, st_d in d.get("reducer", {}).items():
             if name in self.reducer.states:
                 self.reducer.states[name].load_state_dict(st_d)
@@ -405,6 +437,154 @@ def DistributedOptimizer(
                                  max_grad_norm=norm_clip or 0.0,
                                  momentum_correction=momentum_correction,
                                  overlap=overlap)
+
+
+class FlatSGD(_DistributedOptimizer):
+    """SGD (momentum / nesterov / weight decay, no dampening) over flat
+    per-bucket storage, with no inner torch optimizer.
+
+    Buckets, hooks, the reducer thread, `local`, synchronize(), stop() and
+    add_train_epoch() are _DistributedOptimizer's.  Each bucket also owns a
+    flat fp32 copy of its parameters (every p.data is aliased into it, as
+    FlatBertAdam does) and a flat momentum buffer, so the step is ONE fused
+    launch per bucket (ops.sgd_step_) instead of torch's multi-tensor SGD
+    over every parameter tensor.
+
+    Buckets are reduced with sparse_ok=True (OKTOPK_SPARSE_STEP=0 turns it
+    off): where the engine hands a bucket's result over as a SparseGrad,
+    the clip sum and the step (ops.sgd_step_sparse_) consume the selection
+    directly — no zero fill, no scatter, no dense norm read, no gradient
+    read; same bits.  One step may mix sparse and dense buckets.  The
+    all-buckets drain (graph replay, accumulation boundary) keeps the
+    hand-over at world 1 only: at world > 1 it goes through run_many,
+    whose pipeline densifies.
+
+    `param_groups` is one persistent group read at every step, so
+    `g["lr"] = ...` from Trainer.adjust_learning_rate or an external
+    scheduler takes effect on the next step."""
+
+    def __init__(
+        self,
+        named_parameters: Iterable[Tuple[str, torch.Tensor]],
+        comm: Optional[Comm] = None,
+        cfg: Optional[EngineConfig] = None,
+        lr: float = 0.1,
+        momentum: float = 0.9,
+        weight_decay: float = 0.0,
+        nesterov: bool = False,
+        max_grad_norm: float = 0.0,
+        momentum_correction: float = 0.0,
+        overlap: Optional[bool] = None,
+    ):
+        named = [(n, p) for n, p in named_parameters if p.requires_grad]
+        # checked before anything is allocated or aliased, so a caller can
+        # fall back to the torch route with the model untouched
+        for n, p in named:
+            if p.dtype != torch.float32:
+                raise ValueError(
+                    f"FlatSGD needs fp32 parameters; {n} is {p.dtype}")
+            if not p.is_contiguous():
+                raise ValueError(
+                    f"FlatSGD needs contiguous parameters; {n} is not")
+        super().__init__(None, named, comm, cfg, max_grad_norm=max_grad_norm,
+                         momentum_correction=momentum_correction,
+                         overlap=overlap)
+        for b in self.buckets:
+            b.flat_param = torch.empty_like(b.flat)
+            b.momentum_buf = torch.zeros_like(b.flat)
+            for p, (off, n_) in zip(b.params, b.slots):
+                b.flat_param[off : off + n_].copy_(p.data.view(-1))
+                # the module keeps its Parameter objects; .data becomes a view
+                p.data = b.flat_param[off : off + n_].view_as(p)
+        self._groups = [{
+            "lr": float(lr), "momentum": float(momentum),
+            "weight_decay": float(weight_decay), "nesterov": bool(nesterov),
+            "params": [p for _, p in named],
+        }]
+        # buckets x steps that took the sparse route, and the last step's
+        # clip factor (1-elem device tensor, None without clipping)
+        self.sparse_bucket_steps = 0
+        self.last_clip_scale: Optional[torch.Tensor] = None
+
+    @property
+    def _sparse_ok(self) -> bool:
+        return os.environ.get("OKTOPK_SPARSE_STEP", "1") != "0"
+
+    @property
+    def param_groups(self):
+        return self._groups
+
+    @property
+    def state(self):
+        return {b.name: {"flat_param": b.flat_param,
+                         "momentum_buffer": b.momentum_buf}
+                for b in self.buckets}
+
+    def step(self, closure=None):
+        if closure is not None:
+            raise ValueError("FlatSGD.step takes no closure")
+        if not self.local:
+            self.synchronize()
+        g = self._groups[0]
+        lr, mom, wd, nesterov = (g["lr"], g["momentum"], g["weight_decay"],
+                                 g["nesterov"])
+        # each hand-over is consumed once: a step without a reduce (local)
+        # must not see the previous step's selection
+        res = self.reducer.sparse_results
+        sgs = [res.pop(b.name, None) for b in self.buckets]
+        if self.local:
+            sgs = [None] * len(sgs)
+        gscale = None
+        if self.max_grad_norm and self.max_grad_norm > 0:
+            # global-norm clip, device-resident: one fp64 sum of squares
+            # across buckets (over the ~k entries for a sparse bucket), the
+            # factor stays on the device and scales the step's gradient
+            # read — no multiply pass, no host sync
+            dev = self.buckets[0].flat.device
+            acc = torch.zeros(1, dtype=torch.float64, device=dev)
+            for b, sg in zip(self.buckets, sgs):
+                if sg is not None:
+                    ops.sparse_sumsq_into_(acc, sg.idx, sg.val, sg.scale,
+                                           sg.tau, n=b.numel)
+                else:
+                    ops.sumsq_into_(acc, b.flat)
+            gscale = ops.clip_scale_from_sumsq(acc, self.max_grad_norm)
+        self.last_clip_scale = gscale
+        for b, sg in zip(self.buckets, sgs):
+            if sg is not None:
+                ops.sgd_step_sparse_(b.flat_param, sg.idx, sg.val, 0, sg.scale,
+                                     sg.tau, b.momentum_buf, lr, mom, wd,
+                                     nesterov, gscale=gscale)
+                self.sparse_bucket_steps += 1
+            else:
+                ops.sgd_step_(b.flat_param, b.flat, b.momentum_buf, lr, mom,
+                              wd, nesterov, gscale=gscale)
+
+    def state_dict(self):
+        g = self._groups[0]
+        return {
+            "param_group": {k: g[k] for k in
+                            ("lr", "momentum", "weight_decay", "nesterov")},
+            "buckets": {b.name: {"flat_param": b.flat_param,
+                                 "momentum_buf": b.momentum_buf}
+                        for b in self.buckets},
+            "reducer": {
+                name: st.state_dict() for name, st in self.reducer.states.items()
+            },
+        }
+
+    def load_state_dict(self, d):
+        self._groups[0].update(d["param_group"])
+        for b in self.buckets:
+            sd = d["buckets"][b.name]
+            if sd["flat_param"].numel() != b.numel:
+                raise ValueError(f"{b.name}: checkpoint has "
+                                 f"{sd['flat_param'].numel()} elements, the "
+                                 f"model {b.numel}")
+            # copy_ crosses devices (a checkpoint may be mapped elsewhere)
+            b.flat_param.copy_(sd["flat_param"])
+            b.momentum_buf.copy_(sd["momentum_buf"])
+        self._load_reducer_states(d)
 
 
 class FlatBertAdam:

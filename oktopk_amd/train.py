@@ -66,7 +66,7 @@ def build_argparser() -> argparse.ArgumentParser:
     p.add_argument("--dense-warmup", type=int, default=None,
                    help="dense allreduce iterations before sparsifying")
     # optimizer
-    p.add_argument("--optimizer", type=str, default="auto", choices=["auto", "sgd", "adam"])
+    p.add_argument("--optimizer", type=str, default="auto", choices=["auto", "sgd", "adam", "flat_sgd"])
     p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
     # checkpoints (reference --pretrain / per-epoch saves)
     p.add_argument("--checkpoint-dir", type=str, default="")

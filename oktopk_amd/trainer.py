@@ -8,6 +8,7 @@ shapes of the reference configs.
 """
 from __future__ import annotations
 
+import logging
 import os
 from typing import Optional
 
@@ -16,7 +17,9 @@ import torch
 from . import models
 from .comm import Comm
 from .config import EngineConfig
-from .optimizer import DistributedOptimizer, FlatBertAdam
+from .optimizer import DistributedOptimizer, FlatBertAdam, FlatSGD
+
+logger = logging.getLogger("oktopk_amd")
 
 
 _CIFAR = {"vgg11", "vgg13", "vgg16", "vgg19", "resnet20", "resnet32", "resnet44",
@@ -126,7 +129,7 @@ class Trainer:
         device: Optional[torch.device] = None,
         comm: Optional[Comm] = None,
         cfg: Optional[EngineConfig] = None,
-        optimizer: str = "auto",  # auto | sgd | adam
+        optimizer: str = "auto",  # auto | sgd | adam | flat_sgd
         lr: float = None,
         dtype: str = "bf16",
         nsteps_update: int = 1,
@@ -186,8 +189,23 @@ class Trainer:
 
         if optimizer == "auto":
             optimizer = "adam" if model_name.startswith("bert") else "sgd"
+        if optimizer == "sgd" and os.environ.get("OKTOPK_FLAT_SGD", "0") == "1":
+            optimizer = "flat_sgd"
+        if optimizer == "flat_sgd":
+            # same hyper-parameters as the torch route below
+            try:
+                self.opt = FlatSGD(
+                    self.model.named_parameters(), comm=self.comm, cfg=self.cfg,
+                    lr=lr or 0.1, momentum=0.9, weight_decay=5e-4,
+                )
+            except ValueError as e:
+                logger.warning("flat_sgd unavailable (%s); using torch SGD "
+                               "under DistributedOptimizer", e)
+                optimizer = "sgd"
         self.opt_kind = optimizer
-        if optimizer == "adam":
+        if optimizer == "flat_sgd":
+            pass
+        elif optimizer == "adam":
             self.opt = FlatBertAdam(
                 self.model.named_parameters(),
                 comm=self.comm,

@@ -459,10 +459,65 @@ def sparse_step_rows(iters, density=0.001):
     return rows
 
 
+def flat_sgd_rows(iters, sizes=(15_000_000, 27_000_000), density=0.001,
+                  ntensors=60):
+    """The SGD tail at the VGG-16 (15 M) and lstman4 (27 M) scales with
+    k = 0.1 %: sgd_step_ on a dense gradient, the densify (zero fill +
+    scatter) that precedes it, sgd_step_sparse_ on the selection, and
+    torch's foreach SGD over the same storage viewed as `ntensors` parameter
+    tensors.  momentum 0.9, weight decay 5e-4, no clip.  Bytes are the
+    algorithm's, per element: the fused dense step moves 5 streams (20 B),
+    the sparse one 4 (16 B, plus 8 B per entry), the fill 4 B; torch's
+    step as separate passes g + wd*p (12), buf*mom (8), buf + d (12),
+    p - lr*d (12) = 44 B."""
+    g = torch.Generator().manual_seed(0)
+    rows = []
+    for n in sizes:
+        k = int(n * density)
+        idx = torch.randperm(n, generator=g)[:k].sort().values.to(torch.int32).cuda()
+        val = torch.randn(k, generator=g).cuda()
+        p = torch.randn(n, generator=g).cuda()
+        buf = torch.zeros(n, device="cuda")
+        dense = torch.empty(n, device="cuda")
+        H.fill_sparse_scaled_(dense, idx, val, 1.0)
+        hp = (0.1, 0.9, 5e-4, False)
+        cuts = [n * j // ntensors for j in range(ntensors + 1)]
+        params = []
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            q = torch.nn.Parameter(p[a:b])
+            q.grad = dense[a:b]
+            params.append(q)
+        topt = torch.optim.SGD(params, lr=0.1, momentum=0.9, weight_decay=5e-4,
+                               foreach=True)
+        topt.step()  # allocates the momentum buffers
+
+        def torch_route():
+            H.fill_sparse_scaled_(dense, idx, val, 1.0)
+            topt.step()
+
+        def dense_route():
+            H.fill_sparse_scaled_(dense, idx, val, 1.0)
+            H.sgd_step_(p, dense, buf, *hp)
+
+        for name, fn, nbytes in (
+            (f"sgd_step_ n={n}", lambda: H.sgd_step_(p, dense, buf, *hp), 20 * n),
+            (f"fill + sgd_step_ n={n}", dense_route, 24 * n + 12 * k),
+            (f"sgd_step_sparse_ n={n}",
+             lambda: H.sgd_step_sparse_(p, idx, val, 0, 1.0, -1.0, buf, *hp),
+             16 * n + 8 * k),
+            (f"torch foreach SGD n={n}", topt.step, 44 * n),
+            (f"fill + torch foreach n={n}", torch_route, 48 * n + 12 * k),
+        ):
+            dev_us, _wall = time_both(fn, iters)
+            rows.append((name, dev_us / 1000, nbytes / GB / (dev_us / 1e6)))
+        del topt, params, p, buf, dense
+    return rows
+
+
 def print_rows(rows):
-    print(f"{'op':28s} {'ms':>9s} {'GB/s':>8s}")
+    print(f"{'op':36s} {'ms':>9s} {'GB/s':>8s}")
     for name, ms, bw in rows:
-        print(f"{name:28s} {ms:9.4f} {bw:8.0f}")
+        print(f"{name:36s} {ms:9.4f} {bw:8.0f}")
 
 
 def main():
@@ -474,12 +529,15 @@ def main():
                          "round2)")
     ap.add_argument("--only", default="",
                     choices=["", "colsum", "wire", "gauss", "sparse_step",
-                             "topk", "round2"],
+                             "topk", "round2", "flat_sgd"],
                     help="run just one group of rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     if args.only == "sparse_step":
         print_rows(sparse_step_rows(args.iters or 20))
+        return
+    if args.only == "flat_sgd":
+        print_rows(flat_sgd_rows(args.iters or 50))
         return
     if args.only == "colsum":
         print_rows(colsum_rows())
