@@ -392,6 +392,19 @@ class AllReducer:
             torch.cat(vals) if vals else buf[:0].view(torch.float32)
         )
 
+    def _round1_reduce(self, payload, recv_elems, lo: int, hi: int, tau: float,
+                       dev) -> Tuple[torch.Tensor, torch.Tensor]:
+        """device_reduce: the round-1 reduce at this region's owner as one
+        ordered sparse merge.  `payload` is the received wire buffer (with
+        device_wire) or _unpack's (r_idx, r_val); returns the survivors
+        (absolute int32 indices ascending, summed values)."""
+        if self.cfg.oktopk.device_wire:
+            return ops.reduce_segments_wire(payload.to(dev), recv_elems,
+                                            self._wire_bf16, lo, hi - lo, tau)
+        r_idx, r_val = payload
+        return ops.reduce_segments(r_idx.to(dev), r_val.to(dev), recv_elems,
+                                   lo, hi - lo, tau)
+
     # -- Ok-Topk (SURVEY.md section 2.5) --------------------------------
     def _oktopk(self, name: str, t: torch.Tensor, st: TensorState) -> torch.Tensor:
         cfg = self.cfg
@@ -474,7 +487,16 @@ class AllReducer:
 
         s2 = time.perf_counter()
         exact = it % ok.global_threshold_recompute_interval == 0 or st.tau_global <= 0.0
-        if P > 1:
+        if P > 1 and ok.device_reduce:
+            # ordered sparse merge of the received segments: reduce, filter
+            # and "+ lo" in one op, nothing sized by the region
+            gidx, gval = self._round1_reduce(
+                recv if ok.device_wire else (r_idx, r_val), recv_elems, lo, hi,
+                0.0 if exact else st.tau_global, t.device)
+            self._time(name, "reduce", time.perf_counter() - s2)
+            # --- 4. round 2: sparse allgather of the survivors -----------
+            s3 = time.perf_counter()
+        elif P > 1:
             reduced = torch.zeros(hi - lo, dtype=t.dtype, device=t.device)
             if ok.device_wire:
                 # fused unpack-reduce: the payload is never unpacked into
@@ -827,24 +849,35 @@ class AllReducer:
 
         # --- stage 3: reduce + round-2 select + allgather (deferred) -----
         s2 = time.perf_counter()
+        t_reduce = 0.0  # device_reduce: booked under "reduce", not "allgather"
         for c in parts:
             st = c["st"]
             recv = c["w_payload"].wait()
             if not ok.device_wire:
                 r_idx, r_val = self._unpack(recv, c["recv_elems"])
-            reduced = torch.zeros(c["hi_r"] - c["lo_r"],
-                                  dtype=c["sl"].dtype, device=dev)
-            if ok.device_wire:
-                ops.unpack_scatter_add_(reduced, recv.to(dev), c["recv_elems"],
-                                        c["lo_r"], self._wire_bf16)
-            elif r_idx.numel():
-                ops.scatter_add_(reduced, r_idx.to(dev) - c["lo_r"],
-                                 r_val.to(dev))
             exact = c["exact"] = (
                 c["it"] % ok.global_threshold_recompute_interval == 0
                 or st.tau_global <= 0.0)
-            gidx, gval = ops.compact_gt(reduced, 0.0 if exact else st.tau_global)
-            c["gidx"] = gidx + c["lo_r"]
+            tau_g = 0.0 if exact else st.tau_global
+            if ok.device_reduce:
+                sr = time.perf_counter()
+                gidx, gval = self._round1_reduce(
+                    recv if ok.device_wire else (r_idx, r_val),
+                    c["recv_elems"], c["lo_r"], c["hi_r"], tau_g, dev)
+                c["gidx"] = gidx
+                t_reduce += time.perf_counter() - sr
+            else:
+                reduced = torch.zeros(c["hi_r"] - c["lo_r"],
+                                      dtype=c["sl"].dtype, device=dev)
+                if ok.device_wire:
+                    ops.unpack_scatter_add_(reduced, recv.to(dev),
+                                            c["recv_elems"], c["lo_r"],
+                                            self._wire_bf16)
+                elif r_idx.numel():
+                    ops.scatter_add_(reduced, r_idx.to(dev) - c["lo_r"],
+                                     r_val.to(dev))
+                gidx, gval = ops.compact_gt(reduced, tau_g)
+                c["gidx"] = gidx + c["lo_r"]
             c["gval"] = gval
             c["w_gsizes"] = comm.allgather_sizes_async(gidx.numel(), comm.device)
         for c in parts:
@@ -856,7 +889,9 @@ class AllReducer:
                 pack = comm.to_comm(self._pack(c["gidx"], c["gval"]))
             c["w_gather"] = comm.allgatherv_async(
                 pack, [self._pack_ints(x) for x in sizes])
-        self._time(label, "allgather", time.perf_counter() - s2)
+        if ok.device_reduce:
+            self._time(label, "reduce", t_reduce)
+        self._time(label, "allgather", time.perf_counter() - s2 - t_reduce)
 
         # --- stage 4: merge ----------------------------------------------
         s4 = time.perf_counter()

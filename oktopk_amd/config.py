@@ -89,6 +89,21 @@ class OkTopkConfig:
     # multi-GPU step is unmeasured (default off; flip only after the
     # multi-GPU win is measured).
     device_round2: bool = False
+    # Device-side round-1 reduce: at a region owner the received payload —
+    # P rank-ordered, ascending segments — is reduced by one
+    # ops.reduce_segments / ops.reduce_segments_wire call (a P-way merge of
+    # sorted runs with the threshold filter folded in), in place of
+    # zeros(hi - lo) + scatter_add_ / unpack_scatter_add_ + compact_gt +
+    # "+ lo".  The wire form (with device_wire) decodes the received buffer
+    # in the same kernels.  Work is sized by the payload, the dense region
+    # is never allocated, and no float atomic runs: an index with three or
+    # more contributors sums in rank order, as the CPU reference does, so a
+    # world >= 3 step is bit-reproducible.  World 1 has no reduce and is
+    # untouched.  Kernel-level timings against the scatter-add composition
+    # are in profiles/README.md; whether it shortens a real multi-GPU step
+    # is unmeasured (default off; flip only after the multi-GPU win is
+    # measured).
+    device_reduce: bool = False
 
 
 @dataclass

@@ -423,6 +423,79 @@ def round2_tail_wire_(residual: torch.Tensor, idx: torch.Tensor,
     return g_idx, g_val, None if tau is None else float(tau)
 
 
+# -- Ok-Topk round-1 reduce: ordered sparse merge at the region owner ---------
+# The HIP kernels rank every entry by one binary search per other segment, so
+# the device path takes a bounded number of segments; beyond it the torch
+# reference runs on the same device, as for the wire codec.
+
+def reduce_max_segments() -> int:
+    """Largest segment count the HIP reduce takes (RM_MAX_SEG of
+    reduce_merge.hip; the reference has no limit).  Needs the extension."""
+    mod = _load_hip()
+    if mod is None:
+        raise RuntimeError(f"oktopk_amd HIP extension is not built: {_hip_err!r}")
+    return int(mod.reduce_max_segments())
+
+
+def _reduce_backend(t: torch.Tensor, nseg: int):
+    b = _backend(t)
+    if b is not _ref and nseg > b.reduce_max_segments():
+        return _ref
+    return b
+
+
+def _check_reduce_args(name: str, counts, base, length, tau, *i32f32) -> None:
+    for x, dt in i32f32:
+        if x.dtype != dt or x.dim() != 1:
+            raise ValueError(f"{name}: needs 1-D int32 index / wire words "
+                             "and fp32 values")
+        if x.device != i32f32[0][0].device:
+            raise ValueError(f"{name}: device mismatch")
+    if any(c < 0 for c in counts):
+        raise ValueError(f"{name}: negative segment count")
+    if not float(tau) >= 0.0:
+        raise ValueError(f"{name}: tau must be >= 0")
+    if int(length) < 0:
+        raise ValueError(f"{name}: length must be >= 0")
+
+
+def reduce_segments(idx: torch.Tensor, val: torch.Tensor, counts, base: int,
+                    length: int, tau: float):
+    """Round-1 reduce of Ok-Topk at a region owner.  idx (int32) / val
+    (fp32) hold len(counts) concatenated segments in rank order, each
+    ascending and duplicate-free.  Entries with base <= idx < base + length
+    are summed per index in segment order, one fp32 add each — ((v_a + v_b)
+    + v_c) ..., the order of index_add_ on the CPU — and the indices with
+    |sum| > tau (tau >= 0) come back ascending as (g_idx int32, g_val).
+    Bit-equal to zeros(length) + scatter_add_ + compact_gt + base on the
+    CPU; on the GPU nothing of size `length` is touched and no float atomic
+    runs, so the result is the same on every run."""
+    counts = [int(c) for c in counts]
+    _check_reduce_args("reduce_segments", counts, base, length, tau,
+                       (idx, torch.int32), (val, torch.float32))
+    if idx.numel() != val.numel():
+        raise ValueError("reduce_segments: idx / val length mismatch")
+    if sum(counts) != idx.numel():
+        raise ValueError("reduce_segments: counts do not sum to idx.numel()")
+    return tuple(_reduce_backend(idx, len(counts)).reduce_segments(
+        idx, val, counts, int(base), int(length), float(tau)))
+
+
+def reduce_segments_wire(buf: torch.Tensor, counts, wire_bf16: bool, base: int,
+                         length: int, tau: float):
+    """reduce_segments with the segments still packed in the wire layout
+    (`counts`: element counts per segment): bit-equal to reduce_segments
+    over unpack_segments(buf, counts, wire_bf16), decoded in the same
+    kernels on the GPU with no unpacked copy."""
+    counts = [int(c) for c in counts]
+    _check_reduce_args("reduce_segments_wire", counts, base, length, tau,
+                       (buf, torch.int32))
+    if sum(_ref._wire_words(c, bool(wire_bf16)) for c in counts) > buf.numel():
+        raise ValueError("reduce_segments_wire: counts do not fit the buffer")
+    return tuple(_reduce_backend(buf, len(counts)).reduce_segments_wire(
+        buf, counts, bool(wire_bf16), int(base), int(length), float(tau)))
+
+
 def grad_clip_scale(t: torch.Tensor, max_norm: float) -> torch.Tensor:
     """Device-resident clip factor: min(1, max/(||t||+1e-6)) as a 1-elem
     tensor, no host sync (feeds fused_adam_'s gscale)."""

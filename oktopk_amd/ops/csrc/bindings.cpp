@@ -133,6 +133,14 @@ void launch_r2_wire_tail(const int32_t*, const int*, int, int, int, int32_t*,
 void launch_r2_write(const void*, const int32_t*, int64_t, int64_t, int,
                      const uint32_t*, const int*, const int*, const int32_t*,
                      int, float*, int64_t, int32_t*, float*, int, hipStream_t);
+// round-1 reduce as an ordered merge (reduce_merge.hip)
+int reduce_max_segments();
+void rm_heads_geom(int, int*, int*);
+void launch_rm_merge(const int32_t*, const float*, const int*, int, int, int,
+                     int32_t*, float*, hipStream_t);
+void launch_rm_heads(const int32_t*, const float*, int, int, int, int64_t,
+                     int64_t, float, int*, const int*, int32_t*, float*, int,
+                     hipStream_t);
 }
 
 namespace {
@@ -1285,6 +1293,98 @@ static std::tuple<torch::Tensor, torch::Tensor, py::object> round2_tail_wire_(
     return round2_exact(residual, idx, all_idx, all_val, k.value(), hist, true);
 }
 
+// ---------------------------------------------------------------------------
+// Ok-Topk round-1 reduce (reduce_merge.hip): the rank-ordered segments merged
+// by index, equal indices summed in segment order, filtered to
+// [base, base + length) and |sum| > tau.  mode: 0 pair form (ibuf = idx),
+// 1 fp32 wire, 2 bf16 wire (ibuf = buf).  The kept count is the one readback.
+// ---------------------------------------------------------------------------
+static std::vector<torch::Tensor> reduce_run(
+    const torch::Tensor& ibuf, const float* val,
+    const std::vector<int64_t>& counts, int mode, int64_t base, int64_t length,
+    double tau) {
+    const int64_t P = (int64_t)counts.size();
+    TORCH_CHECK(P <= reduce_max_segments(), "reduce_segments: at most ",
+                reduce_max_segments(), " segments, got ", P);
+    TORCH_CHECK(tau >= 0.0, "reduce_segments: tau must be >= 0");
+    TORCH_CHECK(length >= 0, "reduce_segments: length must be >= 0");
+    // [element prefix | index-list word prefix]; the pair form's index lists
+    // are the element prefix itself
+    auto host = torch::empty({2 * (P + 1)}, torch::dtype(torch::kInt32));
+    int32_t* h = host.data_ptr<int32_t>();
+    int64_t M = 0, w = 0;
+    for (int64_t j = 0; j <= P; ++j) {
+        h[j] = (int32_t)M;
+        h[P + 1 + j] = (int32_t)(mode == 0 ? M : w);
+        if (j == P) break;
+        TORCH_CHECK(counts[j] >= 0, "reduce_segments: negative segment count");
+        M += counts[j];
+        w += wire_words(counts[j], mode == 2);
+        TORCH_CHECK(w <= INT32_MAX, "reduce_segments: payload too long");
+    }
+    TORCH_CHECK((mode == 0 ? M : w) <= ibuf.numel(),
+                "reduce_segments: counts need more than the buffer holds");
+    auto iopt = ibuf.options();
+    auto fopt = ibuf.options().dtype(torch::kFloat32);
+    if (M == 0 || length == 0)
+        return {torch::empty({0}, iopt), torch::empty({0}, fopt)};
+    auto meta = host.to(ibuf.device());
+    auto midx = torch::empty({M}, iopt);
+    auto mval = torch::empty({M}, fopt);
+    launch_rm_merge(ibuf.data_ptr<int32_t>(), val, meta.data_ptr<int>(), (int)P,
+                    (int)M, mode, midx.data_ptr<int32_t>(),
+                    mval.data_ptr<float>(), cur_stream());
+    int chunk = 0, nblocks = 0;
+    rm_heads_geom((int)M, &chunk, &nblocks);
+    const int nw = nblocks * 4;
+    auto cnt = torch::empty({nw}, iopt);
+    launch_rm_heads(midx.data_ptr<int32_t>(), mval.data_ptr<float>(), (int)M,
+                    chunk, nblocks, base, length, (float)tau,
+                    cnt.data_ptr<int>(), nullptr, nullptr, nullptr, 0,
+                    cur_stream());
+    auto totals = torch::empty({1}, iopt.dtype(torch::kInt64));
+    launch_count_totals(cnt.data_ptr<int>(), nw, 1, totals.data_ptr<int64_t>(),
+                        cur_stream());
+    const int64_t total = totals.cpu().item<int64_t>();
+    TORCH_CHECK(total >= 0 && total <= M, "reduce_segments: bad kept count");
+    auto g_idx = torch::empty({total}, iopt);
+    auto g_val = torch::empty({total}, fopt);
+    if (total > 0) {
+        auto offs = torch::empty({nw}, iopt);
+        launch_scan_offsets(cnt.data_ptr<int>(), nw, offs.data_ptr<int>(),
+                            cur_stream());
+        launch_rm_heads(midx.data_ptr<int32_t>(), mval.data_ptr<float>(),
+                        (int)M, chunk, nblocks, base, length, (float)tau,
+                        cnt.data_ptr<int>(), offs.data_ptr<int>(),
+                        g_idx.data_ptr<int32_t>(), g_val.data_ptr<float>(),
+                        (int)total, cur_stream());
+    }
+    return {g_idx, g_val};
+}
+
+static std::vector<torch::Tensor> reduce_segments(
+    torch::Tensor idx, torch::Tensor val, std::vector<int64_t> counts,
+    int64_t base, int64_t length, double tau) {
+    check_i32_1d(idx, "idx");
+    check_f32_1d(val, "val");
+    TORCH_CHECK(idx.numel() == val.numel(), "idx / val length mismatch");
+    TORCH_CHECK(val.device() == idx.device(), "val must be on idx's device");
+    int64_t total = 0;
+    for (int64_t c : counts) total += c;
+    TORCH_CHECK(total == idx.numel(), "reduce_segments: counts sum to ", total,
+                ", idx holds ", idx.numel());
+    const at::cuda::CUDAGuard guard(idx.device());
+    return reduce_run(idx, val.data_ptr<float>(), counts, 0, base, length, tau);
+}
+
+static std::vector<torch::Tensor> reduce_segments_wire(
+    torch::Tensor buf, std::vector<int64_t> counts, bool wire_bf16,
+    int64_t base, int64_t length, double tau) {
+    check_i32_1d(buf, "buf");
+    const at::cuda::CUDAGuard guard(buf.device());
+    return reduce_run(buf, nullptr, counts, wire_bf16 ? 2 : 1, base, length, tau);
+}
+
 static std::vector<torch::Tensor> linear_gelu(torch::Tensor x, torch::Tensor w,
                                               torch::Tensor bias, bool apply_gelu,
                                               bool want_pre) {
@@ -1733,6 +1833,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "round2_tail_ over the allgathered wire buffer (decode fused in)",
           py::arg("residual"), py::arg("idx"), py::arg("buf"), py::arg("counts"),
           py::arg("wire_bf16"), py::arg("k") = py::none());
+    m.def("reduce_max_segments", []() { return (int64_t)reduce_max_segments(); },
+          "segment limit of the ordered-merge reduce");
+    m.def("reduce_segments", &reduce_segments,
+          "ordered sparse reduce of rank-ordered ascending segments -> "
+          "(g_idx ascending, g_val) with base <= idx < base + length, |sum| > tau",
+          py::arg("idx"), py::arg("val"), py::arg("counts"), py::arg("base"),
+          py::arg("length"), py::arg("tau"));
+    m.def("reduce_segments_wire", &reduce_segments_wire,
+          "reduce_segments over the packed wire buffer (decode fused in)",
+          py::arg("buf"), py::arg("counts"), py::arg("wire_bf16"),
+          py::arg("base"), py::arg("length"), py::arg("tau"));
     m.def("add_ln_fwd", &add_ln_fwd, "fused y=LN(x+r) forward (bf16)");
     m.def("add_ln_bwd", &add_ln_bwd, "fused add+LN backward (bf16, fp32 col sums)");
     m.def("linear_gelu", &linear_gelu,

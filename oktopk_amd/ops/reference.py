@@ -40,6 +40,8 @@ __all__ = [
     "pack_regions",
     "unpack_segments",
     "unpack_scatter_add_",
+    "reduce_segments",
+    "reduce_segments_wire",
     "colsum_torch_order",
     "attention_ref64",
     "attention_bf16_staged",
@@ -588,6 +590,48 @@ def round2_tail_wire_(residual: torch.Tensor, idx: torch.Tensor,
     k=None is also the returned pair."""
     all_idx, all_val = unpack_segments(buf, counts, wire_bf16)
     return round2_tail_(residual, idx, all_idx, all_val, k)
+
+
+# -- Ok-Topk round-1 reduce at a region owner --------------------------------
+
+def reduce_segments(idx: torch.Tensor, val: torch.Tensor, counts, base: int,
+                    length: int, tau: float):
+    """Reduce of the payload a region owner receives in round 1: `idx`
+    (int32) / `val` (fp32) hold len(counts) concatenated segments in rank
+    order, segment j with counts[j] entries, ascending and duplicate-free.
+
+    This composition is the definition.  Start from `length` zeros; for
+    every entry with base <= idx < base + length add val at idx - base,
+    segments in order and entries within a segment in order, each add one
+    fp32 add (entries outside the range are dropped); keep the positions
+    with |sum| > tau (compact_gt's predicate: exact cancellations and NaN
+    sums go at tau = 0) and return them ascending as (g_idx = position +
+    base int32, g_val = sum fp32).  tau >= 0.
+
+    Reference: reduced_t[indexes - offset] += values over the rank-ordered
+    receive buffers, then compressbythreshold, VGG/allreducer.py:779,794,894."""
+    if tau < 0:
+        raise ValueError("reduce_segments: tau must be >= 0")
+    if length < 0:
+        raise ValueError("reduce_segments: length must be >= 0")
+    if idx.numel() != val.numel() or sum(counts) != idx.numel():
+        raise ValueError("reduce_segments: idx / val / counts length mismatch")
+    reduced = torch.zeros(int(length), dtype=torch.float32, device=val.device)
+    d = idx.long() - int(base)
+    inside = (d >= 0) & (d < int(length))
+    if bool(inside.any()):
+        reduced.index_add_(0, d[inside], val[inside])
+    g_idx, g_val = compact_gt(reduced, float(tau))
+    return g_idx + int(base), g_val
+
+
+def reduce_segments_wire(buf: torch.Tensor, counts, wire_bf16: bool, base: int,
+                         length: int, tau: float):
+    """reduce_segments with the segments still packed in the wire layout
+    (`counts` are ELEMENT counts per segment): bit-equal to reduce_segments
+    over unpack_segments(buf, counts, wire_bf16)."""
+    idx, val = unpack_segments(buf, counts, wire_bf16)
+    return reduce_segments(idx, val, counts, base, length, tau)
 
 
 def grad_clip_scale(t: torch.Tensor, max_norm: float) -> torch.Tensor:

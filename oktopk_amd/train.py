@@ -53,6 +53,10 @@ def build_argparser() -> argparse.ArgumentParser:
                    help="oktopk device-side round-2 tail (global select + "
                         "residual credit in one op, ascending on every "
                         "iteration)")
+    p.add_argument("--device-reduce", action="store_true",
+                   help="oktopk device-side round-1 reduce (ordered sparse "
+                        "merge of the received segments: no dense region, "
+                        "no float atomics)")
     p.add_argument("--device-exact-topk", action="store_true",
                    help="topkA/topkA2/gtopk: device-resident exact top-k "
                         "selection and sparse tree merge instead of "
@@ -107,6 +111,7 @@ def main(argv=None) -> int:
                      balanced_allgather=args.balanced_allgather,
                      device_wire=args.device_wire,
                      device_round2=args.device_round2,
+                     device_reduce=args.device_reduce,
                      gaussian_device_select=args.gaussian_device_select,
                      device_exact_topk=args.device_exact_topk,
                      pipeline_chunks=args.pipeline_chunks)

@@ -23,6 +23,7 @@ setup(
                 "oktopk_amd/ops/csrc/topk_select.hip",
                 "oktopk_amd/ops/csrc/wire_codec.hip",
                 "oktopk_amd/ops/csrc/round2_tail.hip",
+                "oktopk_amd/ops/csrc/reduce_merge.hip",
                 "oktopk_amd/ops/csrc/direct_grad.hip",
                 "oktopk_amd/ops/csrc/ln_bwd.hip",
                 "oktopk_amd/ops/csrc/linear_gelu.hip",

@@ -37,6 +37,9 @@ def main():
     ap.add_argument("--device-round2", action="store_true",
                     help="oktopk round-2 tail (global select + residual "
                          "credit) with the HIP op (OkTopkConfig.device_round2)")
+    ap.add_argument("--device-reduce", action="store_true",
+                    help="oktopk round-1 reduce as the ordered sparse merge "
+                         "HIP op (OkTopkConfig.device_reduce)")
     ap.add_argument("--global-recompute-interval", type=int, default=None,
                     help="override OkTopkConfig.global_threshold_recompute_"
                          "interval (1 makes every oktopk step an exact one)")
@@ -51,7 +54,8 @@ def main():
         cfg = EngineConfig.preset("bert", compressor=comp, density=args.density,
                                   dense_warmup_iters=0,
                                   device_exact_topk=args.device_exact_topk,
-                                  device_round2=args.device_round2)
+                                  device_round2=args.device_round2,
+                                  device_reduce=args.device_reduce)
         if args.global_recompute_interval is not None:
             cfg.oktopk.global_threshold_recompute_interval = \
                 args.global_recompute_interval
@@ -84,6 +88,7 @@ def main():
               f"P={comm.size} steps={args.steps}"
               + (" device_exact_topk" if args.device_exact_topk else "")
               + (" device_round2" if args.device_round2 else "")
+              + (" device_reduce" if args.device_reduce else "")
               + (f" global_recompute_interval={args.global_recompute_interval}"
                  if args.global_recompute_interval is not None else ""))
         print(f"{'compressor':12s} {'ms/step':>9s}  phases(ms)")

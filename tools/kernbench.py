@@ -405,6 +405,93 @@ def round2_rows(reps, sizes=(109_500_000, 336_000_000), density=0.001, P=8):
         del residual, mask
 
 
+def reduce_rows(reps, sizes=(109_500_000, 336_000_000), worlds=(2, 8, 64),
+                densities=(0.001, 0.01)):
+    """Ok-Topk round-1 reduce at a region owner (ops/csrc/reduce_merge.hip)
+    against the composition the engine runs without device_reduce, same
+    process, same inputs, arms alternating: zeros(n / P) + scatter_add_ (pair
+    form) or unpack_scatter_add_ (wire form) + compact_gt + "+ lo" — against
+    one ops.reduce_segments / ops.reduce_segments_wire call.  BERT-base and
+    BERT-large flat sizes, region length n / P, payload P segments of k / P
+    entries: each rank holds about half of a shared hot set of k / P region
+    indices plus private ones, so runs of every length up to P occur.  Values
+    are multiples of 2^-8 (also after the bf16 rounding), so every sum is
+    exact and the two arms are compared for equality before timing despite
+    the baseline's atomics.  tau = 0 (exact iteration) and tau = 1
+    (threshold).  Each call ends in a host readback, so each is timed alone;
+    median and min..max over `reps` repeats."""
+    from oktopk_amd import ops
+
+    print(f"# round-1 reduce, {reps} repeats/row; M = payload entries, "
+          f"kept = survivors")
+    print(f"{'path':74s} {'median ms':>10s} {'min ms':>9s} {'max ms':>9s}")
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for n in sizes:
+        for density in densities:
+            k = max(1, int(n * density))
+            for P in worlds:
+                length = n // P
+                lo = (P // 2) * length
+                c = max(1, k // P)
+                hot = torch.randperm(length, generator=g, device="cuda")[:c]
+                segs = []
+                for _ in range(P):
+                    mine = hot[torch.rand(c, generator=g, device="cuda") < 0.5]
+                    own = torch.randint(0, length, (c - mine.numel(),),
+                                        generator=g, device="cuda")
+                    segs.append((torch.cat([mine, own]).unique() + lo)
+                                .to(torch.int32))
+                counts = [int(s.numel()) for s in segs]
+                idx = torch.cat(segs)
+                M = idx.numel()
+                val = torch.randint(-512, 513, (M,), generator=g,
+                                    device="cuda").float() / 256
+                one = torch.tensor([0, n], dtype=torch.int64)
+                forms = [("pair", None, None)]
+                for wire in ("fp32", "bf16"):
+                    bf = wire == "bf16"
+                    parts, off = [], 0
+                    for cj in counts:
+                        parts.append(ops.pack_regions(
+                            idx[off:off + cj], val[off:off + cj], one, bf)[0])
+                        off += cj
+                    forms.append((wire, torch.cat(parts), bf))
+
+                def scatter_arm(buf, bf, tau):
+                    reduced = torch.zeros(length, device="cuda")
+                    if buf is None:
+                        ops.scatter_add_(reduced, idx - lo, val)
+                    else:
+                        ops.unpack_scatter_add_(reduced, buf, counts, lo, bf)
+                    gi, gv = ops.compact_gt(reduced, tau)
+                    return gi + lo, gv
+
+                def merge_arm(buf, bf, tau):
+                    if buf is None:
+                        return ops.reduce_segments(idx, val, counts, lo, length, tau)
+                    return ops.reduce_segments_wire(buf, counts, bf, lo, length, tau)
+
+                for form, buf, bf in forms:
+                    for mode, tau in (("exact", 0.0), ("threshold", 1.0)):
+                        a = scatter_arm(buf, bf, tau)
+                        b = merge_arm(buf, bf, tau)
+                        assert torch.equal(a[0], b[0]), "indices differ"
+                        assert torch.equal(a[1].view(torch.int32),
+                                           b[1].view(torch.int32)), "sums differ"
+                        times, _ = _alternate(
+                            (("scatter", lambda: scatter_arm(buf, bf, tau)),
+                             ("merge", lambda: merge_arm(buf, bf, tau))),
+                            lambda: None, reps)
+                        for arm, label in (("scatter", "zeros+scatter_add+compact_gt"),
+                                           ("merge", "reduce_segments")):
+                            ts = times[arm]
+                            print(f"{mode:9s} {form:4s} n={n:<10d} P={P:<3d} "
+                                  f"M={M:<8d} kept={a[0].numel():<8d} "
+                                  f"{label:28s} {ts[len(ts) // 2]:10.3f} "
+                                  f"{ts[0]:9.3f} {ts[-1]:9.3f}")
+                del segs, idx, val, forms
+
+
 def sparse_step_rows(iters, density=0.001):
     """The optimizer tail at the 109.5 M flat scale with k = 0.1 %: the dense
     hand-over (zero fill + scatter + dense sum of squares + Adam over p, g,
@@ -525,11 +612,11 @@ def main():
     ap.add_argument("--iters", type=int, default=None,
                     help="calls per timed window (default 20; 1000 for the "
                          "microsecond-scale --only wire rows; repeats per "
-                         "row, default 15, for --only gauss, topk and "
-                         "round2)")
+                         "row, default 15, for --only gauss, topk, "
+                         "round2 and reduce)")
     ap.add_argument("--only", default="",
                     choices=["", "colsum", "wire", "gauss", "sparse_step",
-                             "topk", "round2", "flat_sgd"],
+                             "topk", "round2", "reduce", "flat_sgd"],
                     help="run just one group of rows")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -553,6 +640,9 @@ def main():
         return
     if args.only == "round2":
         round2_rows(args.iters or 15)
+        return
+    if args.only == "reduce":
+        reduce_rows(args.iters or 15)
         return
     args.iters = args.iters or 20
     g = torch.Generator().manual_seed(0)
