@@ -468,8 +468,10 @@ def reduce_segments(idx: torch.Tensor, val: torch.Tensor, counts, base: int,
     + v_c) ..., the order of index_add_ on the CPU — and the indices with
     |sum| > tau (tau >= 0) come back ascending as (g_idx int32, g_val).
     Bit-equal to zeros(length) + scatter_add_ + compact_gt + base on the
-    CPU; on the GPU nothing of size `length` is touched and no float atomic
-    runs, so the result is the same on every run."""
+    CPU for NaN-free sums (a NaN sum is dropped here, float comparison, and
+    kept by compact_gt's bit rule); on the GPU nothing of size `length` is
+    touched and no float atomic runs, so the result is the same on every
+    run."""
     counts = [int(c) for c in counts]
     _check_reduce_args("reduce_segments", counts, base, length, tau,
                        (idx, torch.int32), (val, torch.float32))

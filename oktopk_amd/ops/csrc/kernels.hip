@@ -768,12 +768,16 @@ extern "C" void launch_sgd(float* p, const float* g, float* buf, int64_t n, floa
                        p, g, buf, n, lr, mom, wd, nesterov, mom != 0.f);
 }
 
+// fp32 -> bf16, round to nearest even: torch's cast bit for bit on every
+// non-NaN input.  NaN stays a NaN (sign and upper payload kept, quiet bit
+// set, as wire_f2bf does) — the rounding carry alone would turn payloads
+// like 0x7fffffff into -0.0 and 0x7f800001 into +inf.  The NaN case is a
+// select on the finished 16 bits, after the arithmetic.
 __device__ __forceinline__ short adam_f2b(float f) {
-    union { float f; uint32_t i; } c;
-    c.f = f;
-    uint32_t lsb = (c.i >> 16) & 1;
-    c.i += 0x7fff + lsb;
-    return (short)(c.i >> 16);
+    const uint32_t u = __float_as_uint(f);
+    const uint32_t rne = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    const uint32_t nan = (u >> 16) | 0x0040u;
+    return (short)((u & 0x7fffffffu) > 0x7f800000u ? nan : rne);
 }
 
 __device__ __forceinline__ float adam_one(float pi, float gi, float& mi,

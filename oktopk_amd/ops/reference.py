@@ -48,6 +48,25 @@ __all__ = [
 ]
 
 
+def _abs_bits(x: torch.Tensor) -> torch.Tensor:
+    """|x| as its int32 bit pattern: nonnegative floats order as integers."""
+    return x.contiguous().view(torch.int32) & 0x7FFFFFFF
+
+
+def _sel_gt(x: torch.Tensor, tau: float) -> torch.Tensor:
+    """The selection rule of every thresholded op, as a bool mask: element i
+    is selected iff bits(|x[i]|) > bits(float32(tau)) as unsigned integers;
+    a float32(tau) below zero selects everything, +-0 included (-0.0 itself
+    is not below zero and acts as 0).  NaN is therefore selected at every
+    tau, inf at every finite tau, and subnormals compare exactly — the HIP
+    kernels' sel_gt(abs_bits, tau_to_bits(tau)).  For NaN-free x and tau it
+    is `x.abs() > tau`."""
+    tb = torch.tensor(float(tau), dtype=torch.float64).to(torch.float32)
+    if bool(tb < 0):
+        return torch.ones(x.shape, dtype=torch.bool, device=x.device)
+    return _abs_bits(x) > int(_abs_bits(tb.reshape(1)).item())
+
+
 def kth_abs_value(t: torch.Tensor, k: int) -> float:
     """|t|'s k-th largest value (the exact top-k threshold).
 
@@ -58,21 +77,21 @@ def kth_abs_value(t: torch.Tensor, k: int) -> float:
 
 
 def compact_gt(t: torch.Tensor, tau: float) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Indices (int32, ascending) and values where |t| > tau.
+    """Indices (int32, ascending) and values where |t| > tau (_sel_gt).
 
     Reference: compressbythreshold, VGG/compression.py:122-132."""
     flat = t.reshape(-1)
-    idx = (flat.abs() > tau).nonzero(as_tuple=False).reshape(-1)
+    idx = _sel_gt(flat, tau).nonzero(as_tuple=False).reshape(-1)
     return idx.to(torch.int32), flat[idx]
 
 
 def count_gt(t: torch.Tensor, tau: float) -> int:
-    return int((t.reshape(-1).abs() > tau).sum().item())
+    return int(_sel_gt(t.reshape(-1), tau).sum().item())
 
 
 def count_multi_gt(t: torch.Tensor, taus) -> list:
-    a = t.reshape(-1).abs()
-    return [int((a > float(x)).sum().item()) for x in taus]
+    flat = t.reshape(-1)
+    return [int(_sel_gt(flat, float(x)).sum().item()) for x in taus]
 
 
 def compact_adaptive(t: torch.Tensor, taus, hi_limit: int):
@@ -174,11 +193,6 @@ def gaussian_select_ef(t: torch.Tensor, residual: torch.Tensor, grad,
     tau = cand[chosen]
     idx, val = compact_gt(restored, tau)
     return idx, val, chosen, counts[chosen], tau, tau0, mean, std
-
-
-def _abs_bits(x: torch.Tensor) -> torch.Tensor:
-    """|x| as its int32 bit pattern: nonnegative floats order as integers."""
-    return x.contiguous().view(torch.int32) & 0x7FFFFFFF
 
 
 def topk_select(t: torch.Tensor, k: int):
@@ -364,8 +378,92 @@ def fused_adam_(
     param.add_(update, alpha=-lr)
 
 
+# -- dense Adam: fp64 oracle and rounding bounds ------------------------------
+# The HIP kernel (adam_one in ops/csrc/kernels.hip) receives every
+# hyperparameter as an fp32 scalar and forms 1 - b in fp32:
+#
+#     gi = g*gs                         (gs = *gscale, 1 without one)
+#     m' = m*b1 + c1*gi                 c1 = fp32(1 - b1)
+#     v' = v*b2 + (c2*gi)*gi            c2 = fp32(1 - b2)
+#     p' = p - lr*(m'/(sqrt(v') + eps) + wd*p)
+#
+# adam_ref64 is that formula in fp64 over the same fp32 inputs and the same
+# fp32 hyperparameters.  fused_adam_ above follows torch's convention instead
+# (Python doubles, 1 - b as a double): at b2 = 0.999 its 1 - b2 differs from
+# the kernel's c2 by 1.3e-5 relative, dozens of times the rounding bound on
+# v (tests/test_core_kernels_reference.py measures it).
+
+ADAM_U = 2.0 ** -24       # fp32 unit roundoff
+ADAM_TINY = 2.0 ** -149   # smallest fp32 subnormal: absolute slack
+
+
+def _f32(x) -> float:
+    return float(torch.tensor(float(x), dtype=torch.float64).to(torch.float32))
+
+
+def adam_hyper_f32(lr, b1, b2, eps, wd, gscale=None):
+    """(lr, b1, b2, eps, wd, gs, c1, c2) as the kernel sees them: each
+    rounded to fp32, c = fp32(1 - b) from the rounded b, gs = 1 without a
+    gscale.  Python floats holding fp32 values."""
+    lr, b1, b2, eps, wd = (_f32(x) for x in (lr, b1, b2, eps, wd))
+    gs = 1.0 if gscale is None else _f32(
+        gscale.item() if torch.is_tensor(gscale) else gscale)
+    return lr, b1, b2, eps, wd, gs, _f32(1.0 - b1), _f32(1.0 - b2)
+
+
+def adam_ref64(p, g, m, v, lr, b1, b2, eps, wd, gscale=None):
+    """One Adam step in fp64 on the fp32 inputs, under the kernel's
+    hyperparameter convention.  Writes nothing.  Returns (m64, v64, p_of):
+    the new moments, and a function p_of(m_new, v_new) -> p64 that takes the
+    step from any pair of moments — fed the kernel's own stored m', v', the
+    p check is not charged with the moments' error."""
+    lr, b1, b2, eps, wd, gs, c1, c2 = adam_hyper_f32(lr, b1, b2, eps, wd,
+                                                     gscale)
+    p64, g64 = p.double(), g.double() * gs
+    m64 = m.double() * b1 + c1 * g64
+    v64 = v.double() * b2 + c2 * g64 * g64
+
+    def p_of(m_new, v_new):
+        up = m_new.double() / (v_new.double().sqrt() + eps) + wd * p64
+        return p64 - lr * up
+
+    return m64, v64, p_of
+
+
+def adam_bounds(p, g, m, v, m_new, v_new, lr, b1, b2, eps, wd, gscale=None):
+    """Elementwise bounds (bm, bv, bp), fp64, on |m' - m64|, |v' - v64| and
+    |p' - p_of(m', v')| for a correct fp32 evaluation of the formula above,
+    with u = 2^-24.  Each factor is the number of fp32 roundings on the
+    term's path plus one of slack (which also covers the u^2 terms):
+
+      bm = 4u(|m*b1| + |c1*g*gs|)   g*gs, c1*gi and the sum: 3 roundings on
+                                    the gradient term, 2 on the state term
+      bv = 6u*v64                   g*gs counted twice, c2*gi, *gi, the sum:
+                                    5; every term is non-negative
+      bp = u|p64| + 6u*lr(|m'/(sqrt(v') + eps)| + |wd*p|)
+                                    sqrt, + eps, the division, + wd*p and
+                                    lr*up: 5, and u|p64| for the final
+                                    subtraction
+
+    plus ADAM_TINY (one fp32 subnormal) each, for results that underflow.
+    A fused multiply-add only removes a rounding.  Correctly rounded fp32
+    sqrt and division are assumed (the compiler's default; the build passes
+    no fast-math flag).  m_new, v_new are the moments p' was computed from."""
+    lr, b1, b2, eps, wd, gs, c1, c2 = adam_hyper_f32(lr, b1, b2, eps, wd,
+                                                     gscale)
+    u = ADAM_U
+    p64, g64 = p.double(), g.double() * gs
+    _, v64, p_of = adam_ref64(p, g, m, v, lr, b1, b2, eps, wd, gs)
+    bm = 4 * u * ((m.double() * b1).abs() + (c1 * g64).abs()) + ADAM_TINY
+    bv = 6 * u * v64 + ADAM_TINY
+    step = (m_new.double() / (v_new.double().sqrt() + eps)).abs()
+    bp = (u * p_of(m_new, v_new).abs()
+          + 6 * u * lr * (step + (wd * p64).abs()) + ADAM_TINY)
+    return bm, bv, bp
+
+
 def scatter_gt_credit_(result, residual, idx, val, tau, scale=1.0) -> int:
-    sel = val.abs() > tau
+    sel = _sel_gt(val, tau)
     j = idx.long()[sel]
     result[j] = val[sel] * scale
     residual[j] = 0.0
@@ -375,7 +473,7 @@ def scatter_gt_credit_(result, residual, idx, val, tau, scale=1.0) -> int:
 def credit_gt_(residual, idx, val, tau) -> int:
     """scatter_gt_credit_ without the dense result: residual[idx] = 0 where
     |val| > tau; returns the count."""
-    sel = val.abs() > tau
+    sel = _sel_gt(val, tau)
     residual[idx.long()[sel]] = 0.0
     return int(sel.sum())
 
@@ -386,9 +484,7 @@ def credit_gt_(residual, idx, val, tau) -> int:
 # (tau < 0 keeps every entry) and +0.0 elsewhere.
 
 def _sparse_kept(val: torch.Tensor, tau: float) -> torch.Tensor:
-    if tau < 0:
-        return torch.ones_like(val, dtype=torch.bool)
-    return val.abs() > tau
+    return _sel_gt(val, tau)
 
 
 def densify_sparse_grad(idx, val, base: int, n: int, scale: float, tau: float):
@@ -604,9 +700,10 @@ def reduce_segments(idx: torch.Tensor, val: torch.Tensor, counts, base: int,
     every entry with base <= idx < base + length add val at idx - base,
     segments in order and entries within a segment in order, each add one
     fp32 add (entries outside the range are dropped); keep the positions
-    with |sum| > tau (compact_gt's predicate: exact cancellations and NaN
-    sums go at tau = 0) and return them ascending as (g_idx = position +
-    base int32, g_val = sum fp32).  tau >= 0.
+    with |sum| > tau as a float comparison (exact cancellations and NaN
+    sums go at tau = 0 — for NaN not compact_gt's bit rule, which keeps it;
+    the HIP reduce tests fabsf(s) > tau) and return them ascending as
+    (g_idx = position + base int32, g_val = sum fp32).  tau >= 0.
 
     Reference: reduced_t[indexes - offset] += values over the rank-ordered
     receive buffers, then compressbythreshold, VGG/allreducer.py:779,794,894."""
@@ -621,8 +718,8 @@ def reduce_segments(idx: torch.Tensor, val: torch.Tensor, counts, base: int,
     inside = (d >= 0) & (d < int(length))
     if bool(inside.any()):
         reduced.index_add_(0, d[inside], val[inside])
-    g_idx, g_val = compact_gt(reduced, float(tau))
-    return g_idx + int(base), g_val
+    keep = (reduced.abs() > float(tau)).nonzero(as_tuple=False).reshape(-1)
+    return keep.to(torch.int32) + int(base), reduced[keep]
 
 
 def reduce_segments_wire(buf: torch.Tensor, counts, wire_bf16: bool, base: int,
