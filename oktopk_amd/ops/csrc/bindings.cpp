@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "colsum_exact_config.h"
+#include "grad_batch.h"
 
 // launchers from kernels.hip
 extern "C" {
@@ -988,6 +989,81 @@ static bool colsum_bf16_into_exact(torch::Tensor gy, torch::Tensor dst,
                                     cur_stream()) != 0;
 }
 
+static bool colsum_exact_deferrable(torch::Tensor gy) {
+    // whether a batched colsum entry (small_grads_batched) can take gy: the
+    // same conditions under which colsum_bf16_into_exact launches
+    if (!(gy.is_cuda() && gy.scalar_type() == torch::kBFloat16 &&
+          gy.dim() == 2 && gy.is_contiguous()))
+        return false;
+    const at::cuda::CUDAGuard guard(gy.device());
+    const auto* prop = at::cuda::getCurrentDeviceProperties();
+    auto cfg = colsum_exact::derive(gy.size(0), gy.size(1),
+                                    (uint64_t)(uintptr_t)gy.data_ptr(),
+                                    prop->multiProcessorCount,
+                                    prop->maxThreadsPerMultiProcessor,
+                                    at::cuda::warp_size());
+    return cfg.supported &&
+           colsum_exact_plannable(gy.data_ptr(), gy.size(0), gy.size(1),
+                                  cfg.split ? cfg.bh : 1, cfg.ctas) != 0;
+}
+
+static int64_t small_grads_batched(
+        std::vector<std::tuple<torch::Tensor, torch::Tensor, bool>> entries) {
+    // One launch per GRAD_BATCH_CAPACITY entries (src, dst, is_colsum):
+    //   is_colsum: dst[C] = column sum of src bf16 [R, C], the bits of
+    //              colsum_bf16_into_exact (src must be colsum_exact_deferrable)
+    //   else     : dst[C] += src bf16 [C], the bits of dst.add_(src)
+    // dst is a contiguous bf16 [C] at any element offset; no two entries may
+    // share destination elements.  Returns the number of launches.
+    std::vector<GradBatchItem> items;
+    items.reserve(entries.size());
+    c10::optional<c10::Device> dev;
+    for (auto& [src, dst, is_colsum] : entries) {
+        TORCH_CHECK(src.is_cuda() && src.scalar_type() == torch::kBFloat16 &&
+                    src.is_contiguous() && src.dim() == (is_colsum ? 2 : 1),
+                    "small_grads_batched: src must be contiguous cuda bf16, "
+                    "[R, C] for a colsum entry and [C] for an add entry");
+        const int64_t C = src.size(-1);
+        TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == torch::kBFloat16 &&
+                    dst.is_contiguous() && dst.numel() == C &&
+                    dst.device() == src.device(),
+                    "small_grads_batched: dst must be contiguous cuda bf16 "
+                    "[C] on src's device");
+        if (!dev.has_value()) dev = src.device();
+        TORCH_CHECK(src.device() == *dev,
+                    "small_grads_batched: all entries on one device");
+        if (C == 0) continue;
+        GradBatchItem it{};
+        it.src = src.data_ptr();
+        it.dst = dst.data_ptr();
+        it.C = C;
+        it.is_colsum = is_colsum ? 1 : 0;
+        if (is_colsum) {
+            const at::cuda::CUDAGuard guard(*dev);
+            const auto* prop = at::cuda::getCurrentDeviceProperties();
+            auto cfg = colsum_exact::derive(
+                src.size(0), C, (uint64_t)(uintptr_t)src.data_ptr(),
+                prop->multiProcessorCount, prop->maxThreadsPerMultiProcessor,
+                at::cuda::warp_size());
+            TORCH_CHECK(cfg.supported,
+                        "small_grads_batched: colsum entry outside the ported "
+                        "reduce configuration; check colsum_exact_deferrable");
+            it.R = src.size(0);
+            it.bh = cfg.split ? cfg.bh : 1;
+            it.ctas = cfg.ctas;
+        }
+        items.push_back(it);
+    }
+    if (items.empty()) return 0;
+    const at::cuda::CUDAGuard guard(*dev);
+    const int launches = launch_grad_batch_bf16(items.data(), (int)items.size(),
+                                                cur_stream());
+    TORCH_CHECK(launches >= 0,
+                "small_grads_batched: an entry does not fit the kernel; "
+                "nothing was launched");
+    return launches;
+}
+
 static torch::Tensor linear_bwd_into(torch::Tensor gy, torch::Tensor x,
                                      torch::Tensor w,
                                      c10::optional<torch::Tensor> gw_dst,
@@ -1782,6 +1858,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "dim-0 sum of a contiguous bf16 [R, C], or None",
           py::arg("R"), py::arg("C"), py::arg("src_addr"), py::arg("num_mp"),
           py::arg("max_threads_per_mp"), py::arg("warp_size"));
+    m.def("colsum_exact_deferrable", &colsum_exact_deferrable,
+          "whether small_grads_batched takes gy as a colsum entry");
+    m.def("small_grads_batched", &small_grads_batched,
+          "batched bias column sums and bf16 slot adds: a list of "
+          "(src, dst, is_colsum); returns the number of launches",
+          py::arg("entries"));
+    m.attr("GRAD_BATCH_CAPACITY") = (int64_t)GRAD_BATCH_CAPACITY;
     m.def("ln_bwd_supported", &ln_bwd_into_supported,
           "hidden sizes ln_bwd_into handles");
     m.def("ln_bwd_into", &ln_bwd_into,

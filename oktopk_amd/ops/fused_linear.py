@@ -99,6 +99,7 @@ def fused_linear_gelu(x: torch.Tensor, weight: torch.Tensor, bias=None) -> torch
 
 _SLOT_ATTR = "_oktopk_grad_slot"
 _EVERY_BWD_ATTR = "_oktopk_every_backward"
+_ADD_SLOT_ATTR = "_oktopk_add_slot"
 
 
 def bias_grad_mode() -> str:
@@ -125,12 +126,71 @@ def direct_grad_enabled() -> bool:
     return os.environ.get("OKTOPK_DIRECT_GRAD", "1") != "0"
 
 
+def defer_small_grads_enabled() -> bool:
+    """OKTOPK_DEFER_SMALL_GRADS=0 restores one launch per bias column sum
+    and autograd's own `slot += g` for the LayerNorm gradients."""
+    return os.environ.get("OKTOPK_DEFER_SMALL_GRADS", "1") != "0"
+
+
 class GradSlotOwner:
     """Per-optimizer state the nodes share: ids of the parameters whose slot
-    was written since the last zero_grad()."""
+    was written since the last zero_grad(), and the small gradient writes of
+    the running backward pass that wait for its end.
+
+    Deferred writes.  A bias column sum (first, overwriting write, "exact"
+    mode) and a LayerNorm gamma / beta add are not launched by their node:
+    the node appends (src, slot) here, and one batched launch per
+    GRAD_BATCH_CAPACITY entries (ops/csrc/direct_grad.hip) runs when the
+    backward pass ends, from the autograd engine's end-of-backward callback,
+    on the stream the nodes ran on.  The bits are those of the immediate
+    launches; only their time and number change.  Rules:
+      * `written` is updated when a write is deferred, as if it had run;
+      * a node that finds a pending entry for its parameter (a module used
+        twice in one backward) flushes before an accumulating bias write,
+        and folds a further LayerNorm gradient into the pending one with a
+        bf16 add, which is what autograd's input buffer does;
+      * the list holds its sources alive (the gy of every Linear, ~230 MB at
+        the BERT-base bench shape) until the flush drops them;
+      * discard() forgets entries a failed backward left behind."""
 
     def __init__(self):
         self.written = set()
+        self.pending = []          # (src, dst, is_colsum)
+        self._pending_at = {}      # id(param) -> index into pending
+        self._stream = None
+        self._callback_queued = False
+
+    def has_pending(self, p) -> bool:
+        return id(p) in self._pending_at
+
+    def defer(self, p, src, dst, is_colsum: bool) -> None:
+        at = self._pending_at.get(id(p))
+        if at is not None:
+            # add entries only: callers flush before a second colsum write
+            assert not is_colsum and not self.pending[at][2]
+            self.pending[at] = (self.pending[at][0] + src, dst, False)
+            return
+        self._pending_at[id(p)] = len(self.pending)
+        self.pending.append((src, dst, is_colsum))
+        if not self._callback_queued:
+            self._stream = torch.cuda.current_stream(src.device)
+            torch.autograd.Variable._execution_engine.queue_callback(self.flush)
+            self._callback_queued = True
+
+    def flush(self) -> None:
+        self._callback_queued = False
+        if not self.pending:
+            return
+        from oktopk_amd import _hip_ops
+
+        entries, stream = self.pending, self._stream
+        self.pending, self._pending_at, self._stream = [], {}, None
+        with torch.cuda.stream(stream):
+            _hip_ops.small_grads_batched(entries)
+
+    def discard(self) -> None:
+        self.pending, self._pending_at, self._stream = [], {}, None
+        self._callback_queued = False
 
 
 def mark_every_backward(p: torch.Tensor) -> None:
@@ -152,9 +212,15 @@ def unbind_grad_slot(p: torch.Tensor) -> None:
         delattr(p, _SLOT_ATTR)
 
 
-def _bound_slot(p):
+def bind_add_slot(p: torch.Tensor, slot: torch.Tensor, owner: GradSlotOwner) -> None:
+    """A slot the optimizer still zeroes and a node only ever adds onto (the
+    deferred `slot += g` of SlotLayerNorm): no every-backward promise needed."""
+    setattr(p, _ADD_SLOT_ATTR, (slot, owner))
+
+
+def _bound_slot(p, attr=_SLOT_ATTR):
     """(grad, owner) if p.grad is still the bound slot, else None."""
-    bound = getattr(p, _SLOT_ATTR, None)
+    bound = getattr(p, attr, None)
     if bound is None:
         return None
     slot, owner = bound
@@ -200,6 +266,21 @@ def linear_param_grads(gy, x, w, b, need_w=True, need_b=True, w_shared=False):
     mode = bias_grad_mode()
     bias_kernel, bias_exact = mode == "fast", mode == "exact"
     keys = [id(p) for p, s in ((w, ws), (b, bs)) if s is not None]
+    if bs is not None and owner.has_pending(b):
+        # the bias's first write of this backward still waits: run it before
+        # this one accumulates onto it
+        owner.flush()
+    if (bs is not None and bias_exact and id(b) not in owner.written
+            and defer_small_grads_enabled() and gy.is_contiguous()
+            and _hip_ops.colsum_exact_deferrable(gy2)):
+        # the overwriting bias column sum joins the end-of-backward batch;
+        # gx and gW are computed now, as in the branches below
+        gx = _hip_ops.linear_bwd_into(gy, x, w, ws[0] if ws else None, None,
+                                      id(w) in owner.written, False)
+        owner.defer(b, gy2, bs[0], True)
+        owner.written.update(keys)
+        gw = gy2.t() @ x2 if (need_w and ws is None) else None
+        return gx, gw, None
     accumulate = all(k in owner.written for k in keys)
     if not accumulate and any(k in owner.written for k in keys):
         # mixed state (a bias shared without its weight): one call each

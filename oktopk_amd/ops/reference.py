@@ -43,6 +43,7 @@ __all__ = [
     "reduce_segments",
     "reduce_segments_wire",
     "colsum_torch_order",
+    "slot_add_bf16",
     "attention_ref64",
     "attention_bf16_staged",
 ]
@@ -798,6 +799,17 @@ def colsum_torch_order(x: torch.Tensor, bh: int = 2, ctas: int = 32,
             g = g + P[j]
         G.append(g)
     return tree(G)
+
+
+def slot_add_bf16(dst: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """The add entry of native small_grads_batched, out of place: what the
+    bf16 accumulate `dst += g` leaves.  Both operands are widened to fp32
+    (exact), added once in fp32 (subnormals kept), and the sum is rounded to
+    bf16 to nearest, ties to even.  So -0.0 + +0.0 is +0.0, x + 0.0 is x for
+    every x but -0.0, and a NaN operand gives a NaN."""
+    assert dst.dtype == torch.bfloat16 and g.dtype == torch.bfloat16
+    assert dst.shape == g.shape
+    return (dst.float() + g.float()).to(torch.bfloat16)
 
 
 # -- flash attention --------------------------------------------------------

@@ -12,6 +12,13 @@ ordinary returned gradients.
 
 Opt-in with OKTOPK_DIRECT_LN=1 (see profiles/README.md r03 for the A/B that
 decides the default); only consulted when the model is built.
+
+Without that opt-in, an optimizer that defers small gradient writes
+(GradSlotOwner in fused_linear.py, OKTOPK_DEFER_SMALL_GRADS) binds gamma and
+beta as add slots.  The node then runs torch's own
+native_layer_norm_backward for all three gradients, so every bit is torch's,
+hands autograd no gamma / beta gradient, and leaves the two `slot += g` adds
+to the batched launch at the end of the backward pass.
 """
 from __future__ import annotations
 
@@ -19,7 +26,8 @@ import os
 
 import torch
 
-from .fused_linear import _SLOT_ATTR, _bound_slot
+from .fused_linear import (_ADD_SLOT_ATTR, _SLOT_ATTR, _bound_slot,
+                           defer_small_grads_enabled)
 
 
 def direct_ln_enabled() -> bool:
@@ -54,6 +62,14 @@ class _SlotLayerNormFn(torch.autograd.Function):
         gx, gw, gb = torch.ops.aten.native_layer_norm_backward(
             gy.contiguous(), x, [H], mean, rstd, w, b,
             [bool(need[0]), bool(need[1]), bool(need[2])])
+        if need[1] and need[2] and defer_small_grads_enabled():
+            was, bas = _bound_slot(w, _ADD_SLOT_ATTR), _bound_slot(b, _ADD_SLOT_ATTR)
+            if (was is not None and bas is not None and was[1] is bas[1]
+                    and gw.dtype == torch.bfloat16 and gb.dtype == torch.bfloat16
+                    and gw.is_contiguous() and gb.is_contiguous()):
+                was[1].defer(w, gw, was[0], False)
+                bas[1].defer(b, gb, bas[0], False)
+                return gx, None, None, None
         return gx, gw, gb, None
 
 
@@ -65,6 +81,7 @@ class SlotLayerNorm(torch.nn.LayerNorm):
         if (x.is_cuda and x.dtype == torch.bfloat16 and torch.is_grad_enabled()
                 and self.elementwise_affine and self.bias is not None
                 and len(self.normalized_shape) == 1
-                and hasattr(self.weight, _SLOT_ATTR)):
+                and (hasattr(self.weight, _SLOT_ATTR)
+                     or hasattr(self.weight, _ADD_SLOT_ATTR))):
             return _SlotLayerNormFn.apply(x, self.weight, self.bias, self.eps)
         return super().forward(x)

@@ -699,7 +699,8 @@ class FlatBertAdam:
     _ZERO_MERGE_GAP = 1 << 16  # elements; see _plan_zero_ranges
 
     def _bind_direct_grad(self) -> None:
-        from .ops.fused_linear import (GradSlotOwner, bind_grad_slot,
+        from .ops.fused_linear import (GradSlotOwner, bind_add_slot,
+                                       bind_grad_slot, defer_small_grads_enabled,
                                        direct_grad_enabled, runs_every_backward)
 
         self._dg_owner = None
@@ -713,8 +714,13 @@ class FlatBertAdam:
             if runs_every_backward(p):
                 bind_grad_slot(p, p.grad, owner)
                 self._dg_params.append(p)
+            elif defer_small_grads_enabled():
+                # still zeroed and accumulated onto; a node that knows the
+                # slot (SlotLayerNorm) may batch its `slot += g` with the
+                # other small writes of the backward pass
+                bind_add_slot(p, p.grad, owner)
+        self._dg_owner = owner
         if self._dg_params:
-            self._dg_owner = owner
             self._plan_zero_ranges()
 
     def _plan_zero_ranges(self) -> None:
@@ -773,6 +779,10 @@ class FlatBertAdam:
             self._dg_owner.written.clear()
 
     def zero_grad(self, set_to_none: bool = False):
+        if self._dg_owner is not None:
+            # a completed backward has flushed its deferred writes; whatever
+            # is still listed comes from one that raised
+            self._dg_owner.discard()
         self._settle_direct_grad()
         if self._zero_ranges is None:
             self.flat_grad_model.zero_()
@@ -800,6 +810,9 @@ class FlatBertAdam:
         return [self.current_lr()]
 
     def step(self):
+        if self._dg_owner is not None:
+            assert not self._dg_owner.pending, \
+                "deferred gradient writes left over: a backward did not finish"
         self._settle_direct_grad()
         # 1. sparse allreduce of the whole flat gradient.  The engine may
         # hand the result over in sparse form (AllReducer.run sparse_ok):

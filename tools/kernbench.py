@@ -75,6 +75,46 @@ def colsum_rows():
     return rows
 
 
+def deferred_rows():
+    """The small gradient writes of one BERT-base backward (bs 8, seq 128):
+    52 bias column sums and 52 LayerNorm-gradient adds, launched one by one
+    (colsum_bf16_into_exact, slot.add_) vs small_grads_batched.  Every
+    source is a tensor of its own, as in the backward pass; GB/s counts the
+    bytes the entries read and write."""
+    g = torch.Generator().manual_seed(2)
+    # pooler and NSP head see one row per sequence
+    shapes = ([(8, 768), (1024, 768)]
+              + [(1024, C) for C in (2304, 768, 3072, 768)] * 12
+              + [(8, 2), (1024, 30522)])
+    entries, nbytes = [], 0
+    for R, C in shapes:
+        gy = torch.randn(R, C, generator=g).bfloat16().cuda()
+        dst = torch.zeros(C + 8, dtype=torch.bfloat16, device="cuda")[3:3 + C]
+        assert H.colsum_exact_deferrable(gy)
+        entries.append((gy, dst, True))
+        nbytes += 2 * (R * C + C)
+    for _ in range(52):
+        gv = torch.randn(768, generator=g).bfloat16().cuda()
+        dst = torch.zeros(768 + 8, dtype=torch.bfloat16, device="cuda")[3:3 + 768]
+        entries.append((gv, dst, False))
+        nbytes += 2 * 3 * 768
+
+    def one_by_one():
+        for src, dst, is_colsum in entries:
+            if is_colsum:
+                H.colsum_bf16_into_exact(src, dst, False)
+            else:
+                dst.add_(src)
+
+    rows = []
+    for name, fn in (("small grads one by one (104 launches)", one_by_one),
+                     ("small_grads_batched (2 launches)",
+                      lambda: H.small_grads_batched(entries))):
+        ms = timeit_graph(fn, reps=10) * 1000
+        rows.append((name, ms, nbytes / GB / (ms / 1000)))
+    return rows
+
+
 def time_both(fn, iters, warmup=5):
     """(device us, host wall us) per call over one window of `iters` calls.
     Wall: host clock around the window, ending in a device synchronise.
@@ -615,7 +655,7 @@ def main():
                          "row, default 15, for --only gauss, topk, "
                          "round2 and reduce)")
     ap.add_argument("--only", default="",
-                    choices=["", "colsum", "wire", "gauss", "sparse_step",
+                    choices=["", "colsum", "deferred", "wire", "gauss", "sparse_step",
                              "topk", "round2", "reduce", "flat_sgd"],
                     help="run just one group of rows")
     args = ap.parse_args()
@@ -628,6 +668,9 @@ def main():
         return
     if args.only == "colsum":
         print_rows(colsum_rows())
+        return
+    if args.only == "deferred":
+        print_rows(deferred_rows())
         return
     if args.only == "wire":
         wire_rows(args.iters or 1000)
