@@ -123,16 +123,28 @@ class BertLayer(nn.Module):
         self.drop = nn.Dropout(cfg.hidden_dropout_prob)
 
     def forward(self, x, attn_mask=None):
-        a = self.drop(self.attn(x, attn_mask))
-        x = self._add_ln(x, a, self.ln1)
+        x = self._drop_add_ln(x, self.attn(x, attn_mask), self.ln1)
         h = self._mlp_act(x)
-        o = self.drop(self.fc2(h))
-        x = self._add_ln(x, o, self.ln2)
+        x = self._drop_add_ln(x, self.fc2(h), self.ln2)
         return x
 
+    def _drop_add_ln(self, x, a, ln):
+        # one bit-exact CDNA4 kernel each way for add + LayerNorm and their
+        # backward with the dropout backward (OKTOPK_FUSED_RESIDUAL_LN=0 opts out,
+        # ops/residual_ln.py); the dropout itself stays torch's
+        from ..ops.residual_ln import (residual_dropout_ln, residual_edge,
+                                       residual_ln_available)
+
+        # the previous site's second output, if it left one: the same values
+        # as x on a gradient edge of their own (ops/residual_ln.py)
+        res = residual_edge(x)
+        if residual_ln_available(res, a, ln):
+            return residual_dropout_ln(res, a, ln, self.drop.p, self.drop.training)
+        return self._add_ln(x, self.drop(a), ln)
+
     def _add_ln(self, x, r, ln):
-        # fused residual+LayerNorm CDNA4 kernel on GPU/bf16
-        # (OKTOPK_NO_FUSED_LN=1 opts out); torch path otherwise
+        # the earlier fused residual+LayerNorm kernels (own summation order),
+        # opt-in with OKTOPK_FUSED_LN=1; torch path otherwise
         from ..ops.fused_ln import fused_add_layernorm, fused_ln_available
 
         if fused_ln_available(x):

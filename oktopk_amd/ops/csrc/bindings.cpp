@@ -67,6 +67,16 @@ void launch_ln_bwd_into(const void* gy, const void* x, const void* gamma,
                         const float* mean, const float* rstd, int64_t rows,
                         int64_t H, void* gx, float* ws, void* dgamma,
                         void* dbeta, int accumulate, hipStream_t);
+bool residual_ln_supported(int64_t H);
+void launch_residual_ln_fwd(const void* x, const void* d, const void* gamma,
+                            const void* beta, float eps, void* s, float* mean,
+                            float* rstd, void* y, int64_t rows, int64_t H,
+                            hipStream_t);
+void launch_residual_ln_bwd(const void* gy1, const void* gy2, const void* s,
+                            const float* mean, const float* rstd,
+                            const void* gamma, const void* mask, float scale,
+                            void* gy, void* gs, void* ga, int64_t rows,
+                            int64_t H, hipStream_t);
 void launch_attn_rowdot(const void*, const void*, int64_t, int64_t, int64_t,
                         float*, hipStream_t);
 void launch_linear_gelu(const void*, const void*, const float*, void*, void*, int,
@@ -1570,6 +1580,86 @@ static torch::Tensor ln_bwd_into(torch::Tensor gy, torch::Tensor x,
     return gx;
 }
 
+static bool residual_ln_ok(int64_t H) { return residual_ln_supported(H); }
+
+static bool rln_rows_bf16(const torch::Tensor& t, int64_t H) {
+    return t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
+           t.is_contiguous() && t.dim() >= 1 && t.size(-1) == H &&
+           ((uintptr_t)t.data_ptr() & 7) == 0;
+}
+
+static std::vector<torch::Tensor> residual_ln_fwd(
+        torch::Tensor x, torch::Tensor d, torch::Tensor gamma,
+        torch::Tensor beta, double eps) {
+    // s = x + d, mean / rstd fp32 [rows], y = LN(s): one
+    // launch, torch's bits (residual_ln.hip).  Returns {y, s, mean, rstd}.
+    const int64_t H = x.size(-1);
+    TORCH_CHECK(residual_ln_supported(H), "residual_ln_fwd: unsupported hidden size ", H);
+    TORCH_CHECK(rln_rows_bf16(x, H), "residual_ln_fwd: x must be contiguous cuda bf16, 8-byte aligned");
+    TORCH_CHECK(rln_rows_bf16(d, H) && d.sizes() == x.sizes(),
+                "residual_ln_fwd: d must match x");
+    for (auto* p : {&gamma, &beta})
+        TORCH_CHECK(p->is_cuda() && p->scalar_type() == torch::kBFloat16 &&
+                    p->is_contiguous() && p->numel() == H,
+                    "residual_ln_fwd: gamma / beta must be contiguous bf16 [H]");
+    const at::cuda::CUDAGuard guard(x.device());
+    const int64_t rows = x.numel() / H;
+    auto y = torch::empty_like(x);
+    auto s = torch::empty_like(x);
+    auto mean = torch::empty({rows}, x.options().dtype(torch::kFloat32));
+    auto rstd = torch::empty({rows}, x.options().dtype(torch::kFloat32));
+    launch_residual_ln_fwd(x.data_ptr(), d.data_ptr(),
+                           gamma.data_ptr(), beta.data_ptr(), (float)eps,
+                           s.data_ptr(),
+                           mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                           y.data_ptr(), rows, H, cur_stream());
+    return {y, s, mean, rstd};
+}
+
+static std::vector<torch::Tensor> residual_ln_bwd(
+        torch::Tensor gy1, c10::optional<torch::Tensor> gy2, torch::Tensor s,
+        torch::Tensor mean, torch::Tensor rstd, torch::Tensor gamma,
+        c10::optional<torch::Tensor> mask, double scale) {
+    // Returns {gy, gs, ga}: gy = gy1 + gy2 (gy1 itself without gy2), gs the
+    // LayerNorm input gradient, ga = masked_scale(gs, mask, scale) (gs itself
+    // without a mask).  One launch, torch's bits (residual_ln.hip).
+    const int64_t H = s.size(-1);
+    TORCH_CHECK(residual_ln_supported(H), "residual_ln_bwd: unsupported hidden size ", H);
+    TORCH_CHECK(rln_rows_bf16(s, H) && rln_rows_bf16(gy1, H) &&
+                gy1.numel() == s.numel(),
+                "residual_ln_bwd: gy1 / s must be contiguous cuda bf16, 8-byte aligned");
+    if (gy2.has_value())
+        TORCH_CHECK(rln_rows_bf16(*gy2, H) && gy2->numel() == s.numel(),
+                    "residual_ln_bwd: gy2 must match gy1");
+    const int64_t rows = s.numel() / H;
+    if (mask.has_value())
+        TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == torch::kBool &&
+                    mask->is_contiguous() && mask->numel() == s.numel() &&
+                    ((uintptr_t)mask->data_ptr() & 3) == 0,
+                    "residual_ln_bwd: mask must be a contiguous bool tensor of s's size");
+    TORCH_CHECK(gamma.is_cuda() && gamma.scalar_type() == torch::kBFloat16 &&
+                gamma.is_contiguous() && gamma.numel() == H,
+                "residual_ln_bwd: gamma must be contiguous bf16 [H]");
+    for (auto* p : {&mean, &rstd})
+        TORCH_CHECK(p->is_cuda() && p->scalar_type() == torch::kFloat32 &&
+                    p->is_contiguous() && p->numel() == rows,
+                    "residual_ln_bwd: mean / rstd must be fp32 [rows]");
+    const at::cuda::CUDAGuard guard(s.device());
+    auto gy = gy2.has_value() ? torch::empty_like(s) : gy1;
+    auto gs = torch::empty_like(s);
+    auto ga = mask.has_value() ? torch::empty_like(s) : gs;
+    launch_residual_ln_bwd(gy1.data_ptr(),
+                           gy2.has_value() ? gy2->data_ptr() : nullptr,
+                           s.data_ptr(), mean.data_ptr<float>(),
+                           rstd.data_ptr<float>(), gamma.data_ptr(),
+                           mask.has_value() ? mask->data_ptr() : nullptr,
+                           (float)scale, gy2.has_value() ? gy.data_ptr() : nullptr,
+                           gs.data_ptr(),
+                           mask.has_value() ? ga.data_ptr() : nullptr, rows, H,
+                           cur_stream());
+    return {gy, gs, ga};
+}
+
 static std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, torch::Tensor mask,
                                            int64_t num_heads, double dropout_p,
                                            bool training, bool want_saved) {
@@ -1927,6 +2017,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "reduce_segments over the packed wire buffer (decode fused in)",
           py::arg("buf"), py::arg("counts"), py::arg("wire_bf16"),
           py::arg("base"), py::arg("length"), py::arg("tau"));
+    m.def("residual_ln_supported", &residual_ln_ok,
+          "hidden sizes residual_ln_fwd / residual_ln_bwd handle");
+    m.def("residual_ln_fwd", &residual_ln_fwd,
+          "s = x + d, LayerNorm(s): {y, s, mean, rstd}, torch's bits, one launch");
+    m.def("residual_ln_bwd", &residual_ln_bwd,
+          "gy = gy1 + gy2, LayerNorm input gradient, dropout backward: "
+          "{gy, gs, ga}, torch's bits, one launch");
     m.def("add_ln_fwd", &add_ln_fwd, "fused y=LN(x+r) forward (bf16)");
     m.def("add_ln_bwd", &add_ln_bwd, "fused add+LN backward (bf16, fp32 col sums)");
     m.def("linear_gelu", &linear_gelu,

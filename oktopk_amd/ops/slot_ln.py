@@ -34,6 +34,22 @@ def direct_ln_enabled() -> bool:
     return os.environ.get("OKTOPK_DIRECT_LN", "0") == "1"
 
 
+def defer_ln_param_grads(w, b, gw, gb) -> bool:
+    """Hand torch's gamma / beta gradients to the parameters' add slots, to be
+    added by the batched launch at the end of backward.  False: not bound as
+    add slots of one owner (or deferral is off); return them to autograd."""
+    if not defer_small_grads_enabled():
+        return False
+    was, bas = _bound_slot(w, _ADD_SLOT_ATTR), _bound_slot(b, _ADD_SLOT_ATTR)
+    if (was is not None and bas is not None and was[1] is bas[1]
+            and gw.dtype == torch.bfloat16 and gb.dtype == torch.bfloat16
+            and gw.is_contiguous() and gb.is_contiguous()):
+        was[1].defer(w, gw, was[0], False)
+        bas[1].defer(b, gb, bas[0], False)
+        return True
+    return False
+
+
 class _SlotLayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, eps):
@@ -62,14 +78,8 @@ class _SlotLayerNormFn(torch.autograd.Function):
         gx, gw, gb = torch.ops.aten.native_layer_norm_backward(
             gy.contiguous(), x, [H], mean, rstd, w, b,
             [bool(need[0]), bool(need[1]), bool(need[2])])
-        if need[1] and need[2] and defer_small_grads_enabled():
-            was, bas = _bound_slot(w, _ADD_SLOT_ATTR), _bound_slot(b, _ADD_SLOT_ATTR)
-            if (was is not None and bas is not None and was[1] is bas[1]
-                    and gw.dtype == torch.bfloat16 and gb.dtype == torch.bfloat16
-                    and gw.is_contiguous() and gb.is_contiguous()):
-                was[1].defer(w, gw, was[0], False)
-                bas[1].defer(b, gb, bas[0], False)
-                return gx, None, None, None
+        if need[1] and need[2] and defer_ln_param_grads(w, b, gw, gb):
+            return gx, None, None, None
         return gx, gw, gb, None
 
 

@@ -115,6 +115,49 @@ def deferred_rows():
     return rows
 
 
+def residual_ln_rows():
+    """One post-LN residual site of BERT-base (1024 rows, H 768, dropout 0.1):
+    the forward chain after torch's dropout (add, row moments, normalise) and
+    the backward chain before torch's gamma / beta reduction (accumulate add,
+    LayerNorm input gradient, dropout backward), torch's kernels against
+    residual_ln_fwd / residual_ln_bwd.  gamma and beta sit 4 bytes off an
+    8-byte boundary, as in the flat parameter buffer, so torch runs its
+    row-wise forward kernels.  GB/s counts the bytes the fused kernel moves."""
+    g = torch.Generator().manual_seed(3)
+    R, C = 1024, 768
+    mk = lambda: torch.randn(R, C, generator=g).bfloat16().cuda()
+    x, a, gy1, gy2 = mk(), mk(), mk(), mk()
+    buf = torch.randn(2 * C + 16, generator=g).bfloat16().cuda()
+    gamma, beta = buf[2:2 + C], buf[C + 10:2 * C + 10]
+    d, mask = torch.native_dropout(a, 0.1, True)
+    scale = 1.0 / 0.9
+    y, s, mean, rstd = H.residual_ln_fwd(x, d, gamma, beta, 1e-12)
+    m1, r1 = mean.view(R, 1), rstd.view(R, 1)
+
+    def torch_fwd():
+        torch.native_layer_norm(x + d, (C,), gamma, beta, 1e-12)
+
+    def torch_bwd():
+        gs = torch.ops.aten.native_layer_norm_backward(
+            gy1 + gy2, s, [C], m1, r1, gamma, beta, [True, False, False])[0]
+        torch.ops.aten.native_dropout_backward(gs, mask, scale)
+
+    n = 2 * R * C
+    rows = []
+    for name, fn, nbytes in (
+        ("torch add + moments + apply (3 launches)", torch_fwd, 4 * n),
+        ("residual_ln_fwd (1 launch)",
+         lambda: H.residual_ln_fwd(x, d, gamma, beta, 1e-12), 4 * n),
+        ("torch add + grad_input + masked_scale (3 launches)", torch_bwd, 6.5 * n),
+        ("residual_ln_bwd (1 launch)",
+         lambda: H.residual_ln_bwd(gy1, gy2, s, mean, rstd, gamma, mask, scale),
+         6.5 * n),
+    ):
+        ms = timeit_graph(fn, reps=20) * 1000
+        rows.append((name, ms, nbytes / GB / (ms / 1000)))
+    return rows
+
+
 def time_both(fn, iters, warmup=5):
     """(device us, host wall us) per call over one window of `iters` calls.
     Wall: host clock around the window, ending in a device synchronise.
@@ -655,7 +698,7 @@ def main():
                          "row, default 15, for --only gauss, topk, "
                          "round2 and reduce)")
     ap.add_argument("--only", default="",
-                    choices=["", "colsum", "deferred", "wire", "gauss", "sparse_step",
+                    choices=["", "colsum", "deferred", "residual_ln", "wire", "gauss", "sparse_step",
                              "topk", "round2", "reduce", "flat_sgd"],
                     help="run just one group of rows")
     args = ap.parse_args()
@@ -671,6 +714,9 @@ def main():
         return
     if args.only == "deferred":
         print_rows(deferred_rows())
+        return
+    if args.only == "residual_ln":
+        print_rows(residual_ln_rows())
         return
     if args.only == "wire":
         wire_rows(args.iters or 1000)
