@@ -124,7 +124,7 @@ class BertLayer(nn.Module):
 
     def forward(self, x, attn_mask=None):
         x = self._drop_add_ln(x, self.attn(x, attn_mask), self.ln1)
-        h = self._mlp_act(x)
+        h = F.gelu(self.fc1(x))
         x = self._drop_add_ln(x, self.fc2(h), self.ln2)
         return x
 
@@ -140,25 +140,7 @@ class BertLayer(nn.Module):
         res = residual_edge(x)
         if residual_ln_available(res, a, ln):
             return residual_dropout_ln(res, a, ln, self.drop.p, self.drop.training)
-        return self._add_ln(x, self.drop(a), ln)
-
-    def _add_ln(self, x, r, ln):
-        # the earlier fused residual+LayerNorm kernels (own summation order),
-        # opt-in with OKTOPK_FUSED_LN=1; torch path otherwise
-        from ..ops.fused_ln import fused_add_layernorm, fused_ln_available
-
-        if fused_ln_available(x):
-            return fused_add_layernorm(x, r, ln)
-        return ln(x + r)
-
-    def _mlp_act(self, x):
-        # hand-written MFMA fused GEMM+bias+GELU on GPU/bf16 (reference
-        # LinearActivation fused-gelu, modeling.py:75); torch path otherwise
-        from ..ops.fused_linear import fused_available, fused_linear_gelu
-
-        if fused_available(x, self.fc1.weight):
-            return fused_linear_gelu(x, self.fc1.weight, self.fc1.bias)
-        return F.gelu(self.fc1(x))
+        return ln(x + self.drop(a))
 
 
 class BertModel(nn.Module):

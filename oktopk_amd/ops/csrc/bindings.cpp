@@ -79,17 +79,6 @@ void launch_residual_ln_bwd(const void* gy1, const void* gy2, const void* s,
                             int64_t H, hipStream_t);
 void launch_attn_rowdot(const void*, const void*, int64_t, int64_t, int64_t,
                         float*, hipStream_t);
-void launch_linear_gelu(const void*, const void*, const float*, void*, void*, int,
-                        int, int, int, hipStream_t);
-void launch_add_ln_fwd(const void*, const void*, const void*, const void*, void*,
-                       void*, float*, float*, int64_t, int, float, hipStream_t);
-void launch_add_ln_bwd(const void*, const void*, const float*, const float*,
-                       const void*, void*, float*, float*, int64_t, int,
-                       hipStream_t);
-void launch_attn_fwd(const void*, const void*, void*, void*, void*, int, int,
-                     float, float, unsigned long long, unsigned long long,
-                     const void*, const void*, unsigned int, int, int,
-                     hipStream_t);
 void launch_attn_fwd_fa(const void*, const void*, void*, void*, int, int, int,
                         float, float, unsigned long long, unsigned long long,
                         const void*, const void*, unsigned int, int, int,
@@ -101,7 +90,6 @@ void launch_attn_bwd_fa(const void*, const void*, const void*, const void*,
                         const void*, void*, int, int, int, float, float,
                         unsigned long long, unsigned long long, const void*,
                         const void*, unsigned int, int, int, hipStream_t);
-// launchers from wire_codec.hip
 // gauss_select.hip
 void launch_gauss_moments(const float*, float*, const void*, int64_t, int64_t,
                           int, double*, hipStream_t);
@@ -1471,75 +1459,6 @@ static std::vector<torch::Tensor> reduce_segments_wire(
     return reduce_run(buf, nullptr, counts, wire_bf16 ? 2 : 1, base, length, tau);
 }
 
-static std::vector<torch::Tensor> linear_gelu(torch::Tensor x, torch::Tensor w,
-                                              torch::Tensor bias, bool apply_gelu,
-                                              bool want_pre) {
-    TORCH_CHECK(x.is_cuda() && w.is_cuda(), "GPU tensors required");
-    TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16,
-                "bf16 inputs required");
-    TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1),
-                "x [M,K], w [N,K]");
-    TORCH_CHECK(x.is_contiguous() && w.is_contiguous());
-    TORCH_CHECK(x.size(1) % 32 == 0, "K must be a multiple of 32");
-    const at::cuda::CUDAGuard guard(x.device());
-    int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-    auto y = torch::empty({M, N}, x.options());
-    torch::Tensor z;
-    const float* bptr = nullptr;
-    torch::Tensor bias_f;
-    if (bias.defined() && bias.numel()) {
-        bias_f = bias.to(torch::kFloat32).contiguous();
-        bptr = bias_f.data_ptr<float>();
-    }
-    void* zptr = nullptr;
-    if (want_pre) {
-        z = torch::empty({M, N}, x.options());
-        zptr = z.data_ptr();
-    }
-    launch_linear_gelu(x.data_ptr(), w.data_ptr(), bptr, y.data_ptr(), zptr,
-                       (int)M, (int)N, (int)K, apply_gelu ? 1 : 0, cur_stream());
-    if (want_pre) return {y, z};
-    return {y};
-}
-
-static std::vector<torch::Tensor> add_ln_fwd(torch::Tensor x, torch::Tensor r,
-                                             torch::Tensor gamma, torch::Tensor beta,
-                                             double eps) {
-    TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.is_contiguous());
-    TORCH_CHECK(r.sizes() == x.sizes() && r.is_contiguous());
-    int H = (int)x.size(-1);
-    TORCH_CHECK(H % 128 == 0 && H <= 2048, "H must be a multiple of 128, <= 2048");
-    const at::cuda::CUDAGuard guard(x.device());
-    int64_t rows = x.numel() / H;
-    auto y = torch::empty_like(x);
-    auto s = torch::empty_like(x);
-    auto mean = torch::empty({rows}, x.options().dtype(torch::kFloat32));
-    auto rstd = torch::empty({rows}, x.options().dtype(torch::kFloat32));
-    launch_add_ln_fwd(x.data_ptr(), r.data_ptr(), gamma.contiguous().data_ptr(),
-                      beta.contiguous().data_ptr(), y.data_ptr(), s.data_ptr(),
-                      mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, H,
-                      (float)eps, cur_stream());
-    return {y, s, mean, rstd};
-}
-
-static std::vector<torch::Tensor> add_ln_bwd(torch::Tensor gy, torch::Tensor s,
-                                             torch::Tensor mean, torch::Tensor rstd,
-                                             torch::Tensor gamma) {
-    TORCH_CHECK(gy.is_cuda() && gy.scalar_type() == torch::kBFloat16);
-    int H = (int)gy.size(-1);
-    const at::cuda::CUDAGuard guard(gy.device());
-    int64_t rows = gy.numel() / H;
-    auto gyc = gy.contiguous();
-    auto gx = torch::empty_like(gyc);
-    auto dgamma = torch::zeros({H}, gy.options().dtype(torch::kFloat32));
-    auto dbeta = torch::zeros({H}, gy.options().dtype(torch::kFloat32));
-    launch_add_ln_bwd(gyc.data_ptr(), s.data_ptr(), mean.data_ptr<float>(),
-                      rstd.data_ptr<float>(), gamma.contiguous().data_ptr(),
-                      gx.data_ptr(), dgamma.data_ptr<float>(),
-                      dbeta.data_ptr<float>(), rows, H, cur_stream());
-    return {gx, dgamma, dbeta};
-}
-
 static bool ln_bwd_into_supported(int64_t H) { return ln_bwd_supported(H); }
 
 static torch::Tensor ln_bwd_into(torch::Tensor gy, torch::Tensor x,
@@ -1658,68 +1577,6 @@ static std::vector<torch::Tensor> residual_ln_bwd(
                            mask.has_value() ? ga.data_ptr() : nullptr, rows, H,
                            cur_stream());
     return {gy, gs, ga};
-}
-
-static std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, torch::Tensor mask,
-                                           int64_t num_heads, double dropout_p,
-                                           bool training, bool want_saved) {
-    TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 &&
-                qkv.is_contiguous());
-    TORCH_CHECK(qkv.dim() == 3, "qkv must be [b, s, 3*h]");
-    int64_t B = qkv.size(0), S = qkv.size(1);
-    int64_t H3 = qkv.size(2);
-    int64_t H = H3 / 3;
-    int64_t HD = H / num_heads;
-    TORCH_CHECK(S == 128 && HD == 64, "fused attention specialised for s=128, hd=64");
-    const at::cuda::CUDAGuard guard(qkv.device());
-    auto out = torch::empty({B, S, H}, qkv.options());
-    torch::Tensor p_save, a_save;
-    void* pptr = nullptr;
-    void* aptr = nullptr;
-    if (want_saved) {
-        p_save = torch::empty({B * num_heads, S, S}, qkv.options());
-        a_save = torch::empty({B * num_heads, S, S}, qkv.options());
-        pptr = p_save.data_ptr();
-        aptr = a_save.data_ptr();
-    }
-    const void* mptr = nullptr;
-    torch::Tensor mask_c;
-    if (mask.defined() && mask.numel()) {
-        mask_c = mask.reshape({B, S}).to(torch::kBFloat16).contiguous();
-        mptr = mask_c.data_ptr();
-    }
-    int apply_dropout = (training && dropout_p > 0.0) ? 1 : 0;
-    unsigned long long seed = 0, offset = 0;
-    const void* seed_ptr = nullptr;
-    const void* offset_ptr = nullptr;
-    unsigned int intragraph = 0;
-    int captured = 0;
-    if (apply_dropout) {
-        auto gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
-            c10::nullopt, at::cuda::detail::getDefaultCUDAGenerator());
-        at::PhiloxCudaState state;
-        {
-            std::lock_guard<std::mutex> lock(gen->mutex_);
-            // one philox4x32 block covers 4 elements
-            state = gen->philox_cuda_state((B * num_heads * S * S + 3) / 4 + 1);
-        }
-        if (state.captured_) {
-            captured = 1;
-            seed_ptr = state.seed_.ptr;
-            offset_ptr = state.offset_.ptr;
-            intragraph = state.offset_intragraph_;
-        } else {
-            seed = state.seed_.val;
-            offset = state.offset_.val;
-        }
-    }
-    float scale = 1.0f / std::sqrt((float)HD);
-    launch_attn_fwd(qkv.data_ptr(), mptr, out.data_ptr(), pptr, aptr, (int)B,
-                    (int)num_heads, scale, (float)(1.0 - dropout_p), seed, offset,
-                    seed_ptr, offset_ptr, intragraph, captured, apply_dropout,
-                    cur_stream());
-    if (want_saved) return {out, p_save, a_save};
-    return {out};
 }
 
 static std::vector<torch::Tensor> attn_fwd_fa(torch::Tensor qkv,
@@ -1971,9 +1828,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "flash-bwd D: per-(head,row) dot of gO and O (head_dim 64)");
     m.def("sumsq_into_", &sumsq_into_,
           "accumulate sum(t^2) into a device fp64[1] (no host sync)");
-    m.def("attn_fwd", &attn_fwd,
-          "fused self-attention forward: softmax(QK^T*scale+mask) dropout @ V "
-          "(bf16 MFMA, seq=128/hd=64; returns ctx [+P, A for backward])");
     m.def("attn_fwd_fa", &attn_fwd_fa,
           "flash (online-softmax) attention forward: any seq % 128 == 0, "
           "hd=64 bf16; returns (ctx, lse, philox_state) — O(S) memory");
@@ -2024,8 +1878,4 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("residual_ln_bwd", &residual_ln_bwd,
           "gy = gy1 + gy2, LayerNorm input gradient, dropout backward: "
           "{gy, gs, ga}, torch's bits, one launch");
-    m.def("add_ln_fwd", &add_ln_fwd, "fused y=LN(x+r) forward (bf16)");
-    m.def("add_ln_bwd", &add_ln_bwd, "fused add+LN backward (bf16, fp32 col sums)");
-    m.def("linear_gelu", &linear_gelu,
-          "fused y=gelu(x@W^T+b) bf16 MFMA kernel (optionally returns pre-act)");
 }

@@ -1,71 +1,15 @@
-"""Fused Linear+GELU (hand-written MFMA kernel) with autograd.
+"""Linear layers whose backward writes into the optimizer's gradient slots.
 
-The forward runs the CDNA4 kernel (ops/csrc/linear_gelu.hip): one launch for
-GEMM + bias + erf-GELU, also materialising the pre-activation for backward.
-Backward uses the saved pre-activation for the exact erf-GELU derivative and
-rocBLAS matmuls for the two gradient GEMMs.
-
-Further down: the direct-gradient Linear node (backward writes gW / gb into
-the optimizer's flat gradient buffer, native linear_bwd_into) and
-ColsumLinear, the nn.Linear every BERT site uses.
-
-Parity: the reference's LinearActivation fused-gelu module
-(/root/reference/BERT/bert/transformers/modeling.py:75).
+The direct-gradient Linear node: backward writes gW / gb straight into the
+optimizer's flat gradient buffer (native linear_bwd_into), and ColsumLinear,
+the nn.Linear every BERT site uses, which routes through that node when its
+parameters are bound to gradient slots.
 """
 from __future__ import annotations
 
 import os
 
 import torch
-
-_SQRT1_2 = 0.7071067811865476
-_INV_SQRT_2PI = 0.3989422804014327
-
-
-def fused_available(x: torch.Tensor, weight: torch.Tensor) -> bool:
-    # opt-in: at BERT-base shapes (M=1024, 192 blocks) the correctness-tier
-    # kernel underfills 256 CUs and loses ~1ms/step to hipBLASLt+gelu
-    # (measured); enable for A/B with OKTOPK_FUSED_MLP=1
-    if os.environ.get("OKTOPK_FUSED_MLP", "0") != "1":
-        return False
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16):
-        return False
-    if weight.shape[1] % 32 != 0:
-        return False
-    from . import hip_available
-
-    return hip_available()
-
-
-class _FusedLinearGelu(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        from oktopk_amd import _hip_ops
-
-        shp = x.shape
-        x2 = x.reshape(-1, shp[-1]).contiguous()
-        b = bias if bias is not None else torch.empty(0, device=x.device)
-        y, z = _hip_ops.linear_gelu(x2, weight.contiguous(), b, True, True)
-        ctx.save_for_backward(x2, weight, z, bias)
-        ctx.in_shape = shp
-        return y.reshape(*shp[:-1], weight.shape[0])
-
-    @staticmethod
-    def backward(ctx, gy):
-        x2, w, z, b = ctx.saved_tensors
-        gy2 = gy.reshape(-1, gy.shape[-1])
-        zf = z.float()
-        # d/dz gelu_erf(z) = Phi(z) + z * phi(z)
-        gp = 0.5 * (1.0 + torch.erf(zf * _SQRT1_2)) + zf * torch.exp(-0.5 * zf * zf) * _INV_SQRT_2PI
-        gpre = (gy2.float() * gp).to(gy2.dtype)
-        gx, gw, gb = linear_param_grads(gpre, x2, w, b, ctx.needs_input_grad[1],
-                                        b is not None and ctx.needs_input_grad[2])
-        return gx.reshape(ctx.in_shape), gw, gb
-
-
-def fused_linear_gelu(x: torch.Tensor, weight: torch.Tensor, bias=None) -> torch.Tensor:
-    """y = gelu(x @ weight^T + bias), bf16, single MFMA kernel forward."""
-    return _FusedLinearGelu.apply(x, weight, bias)
 
 
 # ---------------------------------------------------------------------------

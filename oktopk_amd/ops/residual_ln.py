@@ -19,7 +19,7 @@ apart and the kernel adds them; where only one arrives it takes that one.
 
 On by default; OKTOPK_FUSED_RESIDUAL_LN=0 restores the unfused path (read at
 each call; profiles/README.md r15 has the A/B).  Not taken with
-OKTOPK_FUSED_LN=1 or OKTOPK_DIRECT_LN=1, nor where torch itself would run
+OKTOPK_DIRECT_LN=1, nor where torch itself would run
 another kernel: its vectorised LayerNorm forward, which sums in another order,
 is what torch launches when x, gamma and beta are all 8-byte aligned, so the
 fused path needs gamma or beta off that alignment.  That hinges on the layout
@@ -43,7 +43,6 @@ from .slot_ln import defer_ln_param_grads
 def residual_ln_enabled() -> bool:
     env = os.environ
     return (env.get("OKTOPK_FUSED_RESIDUAL_LN", "1") != "0"
-            and env.get("OKTOPK_FUSED_LN", "0") != "1"
             and env.get("OKTOPK_DIRECT_LN", "0") != "1")
 
 

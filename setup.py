@@ -27,9 +27,6 @@ setup(
                 "oktopk_amd/ops/csrc/direct_grad.hip",
                 "oktopk_amd/ops/csrc/ln_bwd.hip",
                 "oktopk_amd/ops/csrc/residual_ln.hip",
-                "oktopk_amd/ops/csrc/linear_gelu.hip",
-                "oktopk_amd/ops/csrc/add_layernorm.hip",
-                "oktopk_amd/ops/csrc/attention.hip",
                 "oktopk_amd/ops/csrc/attention_fa.hip",
             ],
             extra_compile_args={

@@ -4,7 +4,6 @@ hand-over on vs off (OKTOPK_SPARSE_STEP) — parameters and momentum must not
 change by a bit, on buckets that take the hand-over and on buckets that fall
 back alike — plus its optimizer surface: param_groups, state_dict, the
 fp32-only check and the Trainer / environment selection."""
-import os
 
 import pytest
 import torch
@@ -167,8 +166,8 @@ def _train_cnn(sparse_step, max_grad_norm=0.0):
     from oktopk_amd.optimizer import FlatSGD
     from oktopk_amd.trainer import Trainer
 
-    os.environ["OKTOPK_SPARSE_STEP"] = sparse_step
-    try:
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("OKTOPK_SPARSE_STEP", sparse_step)
         torch.manual_seed(0)
         tr = Trainer("mnistnet", batch_size=8, cfg=_cfg(), dtype="fp32",
                      optimizer="flat_sgd", lr=LR, device=torch.device("cpu"))
@@ -182,8 +181,6 @@ def _train_cnn(sparse_step, max_grad_norm=0.0):
             snaps.append(_snap(opt))
             if max_grad_norm:
                 factors.append(float(opt.last_clip_scale))
-    finally:
-        os.environ.pop("OKTOPK_SPARSE_STEP", None)
     return opt, snaps, factors
 
 
@@ -220,8 +217,8 @@ def _mlp(seed=3, width=64, layers=4):
 def _train_mlp(comm, rank, sparse_step, steps=_STEPS, **kw):
     from oktopk_amd.optimizer import FlatSGD
 
-    os.environ["OKTOPK_SPARSE_STEP"] = sparse_step
-    try:
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("OKTOPK_SPARSE_STEP", sparse_step)
         model = _mlp()
         cfg = _cfg()
         cfg.density = 0.05
@@ -237,8 +234,6 @@ def _train_mlp(comm, rank, sparse_step, steps=_STEPS, **kw):
             torch.nn.functional.cross_entropy(model(x), y).backward()
             opt.step()
         opt.stop()
-    finally:
-        os.environ.pop("OKTOPK_SPARSE_STEP", None)
     return opt, model
 
 
@@ -275,8 +270,8 @@ def test_flat_sgd_all_buckets_drain_keeps_hand_over_at_world1():
     from oktopk_amd.optimizer import FlatSGD
 
     def run(sparse_step):
-        os.environ["OKTOPK_SPARSE_STEP"] = sparse_step
-        try:
+        with pytest.MonkeyPatch.context() as mp:
+            mp.setenv("OKTOPK_SPARSE_STEP", sparse_step)
             model = _mlp()
             cfg = _cfg()
             cfg.density, cfg.bucket_bytes = 0.05, 8 << 10
@@ -290,8 +285,6 @@ def test_flat_sgd_all_buckets_drain_keeps_hand_over_at_world1():
                 torch.nn.functional.cross_entropy(model(x), y).backward()
                 opt.local = False
                 opt.step()
-        finally:
-            os.environ.pop("OKTOPK_SPARSE_STEP", None)
         return opt
 
     on, off = run("1"), run("0")

@@ -170,7 +170,7 @@ class Arm:
 
         monkeypatch.setenv("OKTOPK_FUSED_RESIDUAL_LN", "1" if fused else "0")
         monkeypatch.setenv("OKTOPK_DEFER_SMALL_GRADS", "1")
-        for k in ("OKTOPK_FUSED_LN", "OKTOPK_DIRECT_LN", "OKTOPK_COLSUM_BIAS"):
+        for k in ("OKTOPK_DIRECT_LN", "OKTOPK_COLSUM_BIAS"):
             monkeypatch.delenv(k, raising=False)
         torch.manual_seed(11)
         self.model = TinyBert(hidden, heads, p).to(dtype).cuda().train()
@@ -339,9 +339,6 @@ def test_eligibility_switches_and_alignment(monkeypatch):
     ln = arm.model.layer[0].ln1
     x = torch.randn(4, 768, device="cuda").to(BF)
     assert residual_ln_available(x, x.clone(), ln)
-    monkeypatch.setenv("OKTOPK_FUSED_LN", "1")
-    assert not residual_ln_available(x, x.clone(), ln)
-    monkeypatch.delenv("OKTOPK_FUSED_LN")
     monkeypatch.setenv("OKTOPK_DIRECT_LN", "1")
     assert not residual_ln_available(x, x.clone(), ln)
     monkeypatch.delenv("OKTOPK_DIRECT_LN")

@@ -3,7 +3,6 @@ CPU: the torch references against a brute-force composition, the wire form
 against the pair form, the engine with OkTopkConfig.device_round2 against the
 host composition over gloo, and the sparse hand-over on exact iterations.
 Every comparison is bit for bit."""
-import os
 
 import pytest
 import torch
@@ -351,8 +350,8 @@ def _train(comm, sparse_step):
     after every step."""
     from oktopk_amd.trainer import Trainer
 
-    os.environ["OKTOPK_SPARSE_STEP"] = sparse_step
-    try:
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("OKTOPK_SPARSE_STEP", sparse_step)
         torch.manual_seed(0)
         cfg = EngineConfig.preset(
             "bert", compressor="oktopk", density=0.01, dense_warmup_iters=0,
@@ -368,8 +367,6 @@ def _train(comm, sparse_step):
             snaps.append((opt.flat_param.clone(), opt.exp_avg.clone(),
                           opt.exp_avg_sq.clone(),
                           opt.reducer.states["flat"].residual.clone()))
-    finally:
-        os.environ.pop("OKTOPK_SPARSE_STEP", None)
     assert tr.opt.reducer.states["flat"].mask is None
     return took, snaps
 

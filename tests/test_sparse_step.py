@@ -2,7 +2,6 @@
 the dense route, and FlatBertAdam with the sparse hand-over on vs off
 (OKTOPK_SPARSE_STEP) — parameters and Adam state must not change by a bit,
 on steps that take the hand-over and on steps that fall back alike."""
-import os
 
 import pytest
 import torch
@@ -95,8 +94,8 @@ def _train(comm, sparse_step):
     5: hand-over), and a local-threshold recompute (4) in between."""
     from oktopk_amd.trainer import Trainer
 
-    os.environ["OKTOPK_SPARSE_STEP"] = sparse_step
-    try:
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("OKTOPK_SPARSE_STEP", sparse_step)
         torch.manual_seed(0)
         cfg = EngineConfig.preset(
             "bert", compressor="oktopk", density=0.01, dense_warmup_iters=0,
@@ -108,8 +107,6 @@ def _train(comm, sparse_step):
         for _ in range(_STEPS):
             tr.step()
             took.append(tr.opt.reducer.sparse_result is not None)
-    finally:
-        os.environ.pop("OKTOPK_SPARSE_STEP", None)
     opt = tr.opt
     return took, (opt.flat_param.clone(), opt.exp_avg.clone(),
                   opt.exp_avg_sq.clone(),

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Attention A/B: flash kernel (attention_fa.hip) vs torch SDPA (AOTriton)
-vs the legacy seq-128 kernel vs the eager matmul chain — fwd-only and
+vs the eager matmul chain — fwd-only and
 fwd+bwd, BERT-base head shapes at seq 128/256/512 (VERDICT r01 item 8:
 "an A/B table like r01-f").
 
@@ -36,7 +36,7 @@ def make_qkv(b, s, nh, hd, grad):
 
 
 def run_shape(b, s, nh, hd, iters, dropout_p):
-    from oktopk_amd.ops.fused_attn import _FlashAttention, _FusedAttention
+    from oktopk_amd.ops.fused_attn import _FlashAttention
 
     res = {}
     scale = 1.0 / math.sqrt(hd)
@@ -62,9 +62,6 @@ def run_shape(b, s, nh, hd, iters, dropout_p):
         "flash(ours)": lambda qkv: _FlashAttention.apply(
             qkv, None, nh, dropout_p, True),
     }
-    if s == 128:
-        variants["legacy(ours)"] = lambda qkv: _FusedAttention.apply(
-            qkv, None, nh, dropout_p, True)
 
     for name, fn in variants.items():
         qkv = make_qkv(b, s, nh, hd, grad=False)
