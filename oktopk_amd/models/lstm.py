@@ -9,6 +9,8 @@ import math
 import torch
 import torch.nn as nn
 
+from ..ops.hip_lstm import hip_lstm_available, hip_lstm_enabled, lstm_layer
+
 
 class BatchRNN(nn.Module):
     """One LSTM layer with BN on input; bidirectional variants sum the two
@@ -30,11 +32,25 @@ class BatchRNN(nn.Module):
         if self.batch_norm is not None:
             t, n = x.size(0), x.size(1)
             x = self.batch_norm(x.view(t * n, -1)).view(t, n, -1)
+        if hip_lstm_enabled() and hip_lstm_available(x, self.rnn):
+            return self._hip_lstm(x)
         x, _ = self.rnn(x)
         if self.bidirectional:
             # sum forward/backward directions (reference BatchRNN)
             x = x.view(x.size(0), x.size(1), 2, -1).sum(2)
         return x
+
+    def _hip_lstm(self, x: torch.Tensor) -> torch.Tensor:
+        """The layer on ops/hip_lstm.py's kernels (OKTOPK_HIP_LSTM=1), read
+        from self.rnn's parameters: one call per direction, summed."""
+        r = self.rnn
+        y = lstm_layer(x, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0,
+                       r.bias_hh_l0)
+        if self.bidirectional:
+            y = y + lstm_layer(x, r.weight_ih_l0_reverse, r.weight_hh_l0_reverse,
+                               r.bias_ih_l0_reverse, r.bias_hh_l0_reverse,
+                               reverse=True)
+        return y
 
 
 class DeepSpeech(nn.Module):

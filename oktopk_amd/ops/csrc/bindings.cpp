@@ -140,6 +140,12 @@ void launch_rm_merge(const int32_t*, const float*, const int*, int, int, int,
 void launch_rm_heads(const int32_t*, const float*, int, int, int, int64_t,
                      int64_t, float, int*, const int*, int32_t*, float*, int,
                      hipStream_t);
+// fused LSTM recurrent step (lstm_cell.hip)
+void launch_lstm_fwd(float* gx, const float* w_hh, float* y, float* c, int T,
+                     int N, int H, int reverse, hipStream_t);
+void launch_lstm_bwd(const float* gy, const float* act, const float* c,
+                     const float* w_hh_t, float* dc_carry, float* dgates, int T,
+                     int N, int H, int reverse, hipStream_t);
 }
 
 namespace {
@@ -1579,6 +1585,76 @@ static std::vector<torch::Tensor> residual_ln_bwd(
     return {gy, gs, ga};
 }
 
+// -- fused LSTM recurrent step (lstm_cell.hip) --------------------------------
+
+static void check_lstm_3d(const torch::Tensor& t, int64_t T, int64_t N,
+                          int64_t last, const char* name) {
+    check_f32_1d(t, name);
+    TORCH_CHECK(t.dim() == 3 && t.size(0) == T && t.size(1) == N &&
+                    t.size(2) == last,
+                name, " must be [", T, ", ", N, ", ", last, "]");
+}
+
+static std::vector<torch::Tensor> lstm_fwd(torch::Tensor gx, torch::Tensor w_hh,
+                                           bool reverse) {
+    // gx [T, N, 4H]: x @ W_ih^T + b_ih + b_hh in, the activations (i, f, g, o)
+    // out, in place.  Zero initial state.  Returns {y, c}, both [T, N, H].
+    // T launches on the current stream, nothing read back: capturable.
+    check_f32_1d(gx, "gx");
+    check_f32_1d(w_hh, "w_hh");
+    TORCH_CHECK(gx.dim() == 3 && w_hh.dim() == 2, "gx [T, N, 4H], w_hh [4H, H]");
+    const int64_t T = gx.size(0), N = gx.size(1), H = w_hh.size(1);
+    TORCH_CHECK(T >= 1 && N >= 1 && H >= 4 && H % 4 == 0,
+                "lstm_fwd: needs T >= 1, N >= 1 and H a positive multiple of 4");
+    TORCH_CHECK(gx.size(2) == 4 * H && w_hh.size(0) == 4 * H,
+                "lstm_fwd: gx [T, N, 4H] and w_hh [4H, H] disagree on H");
+    TORCH_CHECK(w_hh.device() == gx.device(), "lstm_fwd: device mismatch");
+    TORCH_CHECK(N * 4 * H < ((int64_t)1 << 31) && N <= 16 * 65535 &&
+                    T < ((int64_t)1 << 31),
+                "lstm_fwd: shape too large");
+    const at::cuda::CUDAGuard guard(gx.device());
+    auto y = torch::empty({T, N, H}, gx.options());
+    auto c = torch::empty({T, N, H}, gx.options());
+    launch_lstm_fwd(gx.data_ptr<float>(), w_hh.data_ptr<float>(),
+                    y.data_ptr<float>(), c.data_ptr<float>(), (int)T, (int)N,
+                    (int)H, reverse ? 1 : 0, cur_stream());
+    return {y, c};
+}
+
+static torch::Tensor lstm_bwd(torch::Tensor gy, torch::Tensor act,
+                              torch::Tensor c, torch::Tensor y,
+                              torch::Tensor w_hh_t, bool reverse) {
+    // dgates [T, N, 4H]: the gradient at the pre-activation gates, from gy
+    // (the gradient at y), lstm_fwd's activations and c, and W_hh^T [H, 4H].
+    // The steps recompute tanh(c_t), so y only fixes the shapes.
+    TORCH_CHECK(y.dim() == 3, "lstm_bwd: y must be [T, N, H]");
+    const int64_t T = y.size(0), N = y.size(1), H = y.size(2);
+    TORCH_CHECK(T >= 1 && N >= 1 && H >= 4 && H % 4 == 0,
+                "lstm_bwd: needs T >= 1, N >= 1 and H a positive multiple of 4");
+    check_lstm_3d(y, T, N, H, "y");
+    check_lstm_3d(gy, T, N, H, "gy");
+    check_lstm_3d(c, T, N, H, "c");
+    check_lstm_3d(act, T, N, 4 * H, "act");
+    check_f32_1d(w_hh_t, "w_hh_t");
+    TORCH_CHECK(w_hh_t.dim() == 2 && w_hh_t.size(0) == H &&
+                    w_hh_t.size(1) == 4 * H,
+                "lstm_bwd: w_hh_t must be [H, 4H]");
+    for (auto* p : {&gy, &c, &y, &w_hh_t})
+        TORCH_CHECK(p->device() == act.device(), "lstm_bwd: device mismatch");
+    TORCH_CHECK(N * 4 * H < ((int64_t)1 << 31) && N <= 16 * 65535 &&
+                    T < ((int64_t)1 << 31),
+                "lstm_bwd: shape too large");
+    const at::cuda::CUDAGuard guard(act.device());
+    auto dgates = torch::empty_like(act);
+    // written by the first step before any step reads it
+    auto dc_carry = torch::empty({N, H}, act.options());
+    launch_lstm_bwd(gy.data_ptr<float>(), act.data_ptr<float>(),
+                    c.data_ptr<float>(), w_hh_t.data_ptr<float>(),
+                    dc_carry.data_ptr<float>(), dgates.data_ptr<float>(), (int)T,
+                    (int)N, (int)H, reverse ? 1 : 0, cur_stream());
+    return dgates;
+}
+
 static std::vector<torch::Tensor> attn_fwd_fa(torch::Tensor qkv,
                                               torch::Tensor mask,
                                               int64_t num_heads,
@@ -1878,4 +1954,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("residual_ln_bwd", &residual_ln_bwd,
           "gy = gy1 + gy2, LayerNorm input gradient, dropout backward: "
           "{gy, gs, ga}, torch's bits, one launch");
+    m.def("lstm_fwd", &lstm_fwd,
+          "fp32 LSTM time loop, zero initial state: gx [T, N, 4H] -> "
+          "activations in place; returns {y, c}; one launch per step",
+          py::arg("gx"), py::arg("w_hh"), py::arg("reverse"));
+    m.def("lstm_bwd", &lstm_bwd,
+          "backward of lstm_fwd's time loop: dgates [T, N, 4H]; one launch "
+          "per step",
+          py::arg("gy"), py::arg("act"), py::arg("c"), py::arg("y"),
+          py::arg("w_hh_t"), py::arg("reverse"));
 }

@@ -46,6 +46,7 @@ __all__ = [
     "slot_add_bf16",
     "attention_ref64",
     "attention_bf16_staged",
+    "lstm_layer_ref",
 ]
 
 
@@ -1033,3 +1034,38 @@ def attn_lse_bound(lse64: torch.Tensor) -> torch.Tensor:
     a = lse64.abs().float()
     ulp = (torch.nextafter(a, torch.full_like(a, float("inf"))) - a).double()
     return torch.clamp(2.0 * ulp, min=2.0 ** -10)
+
+
+# -- LSTM layer -----------------------------------------------------------------
+
+def lstm_layer_ref(x, w_ih, w_hh, b_ih, b_hh, reverse: bool = False):
+    """One LSTM direction with zero initial state as a torch loop over time:
+    x [T, N, F] -> y [T, N, H], torch's gate order (i, f, g, o as row blocks
+    of w_ih [4H, F] / w_hh [4H, H]); `reverse` walks time from T-1 to 0.
+    Differentiable, in the dtype it is given: the CPU path of
+    ops.hip_lstm.lstm_layer, its fp32 yardstick and, in fp64, its oracle."""
+    T, N, _ = x.shape
+    H = w_hh.shape[1]
+    gx = (x.reshape(T * N, -1) @ w_ih.t() + (b_ih + b_hh)).view(T, N, 4 * H)
+    h = x.new_zeros(N, H)
+    c = x.new_zeros(N, H)
+    ys = [None] * T
+    for t in (range(T - 1, -1, -1) if reverse else range(T)):
+        i, f, g, o = (gx[t] + h @ w_hh.t()).chunk(4, dim=1)
+        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+        h = torch.sigmoid(o) * torch.tanh(c)
+        ys[t] = h
+    return torch.stack(ys)
+
+
+# A kernel result passes when its rel_fro against the fp64 oracle, per tensor,
+# is at most this many times that of lstm_layer_ref in fp32 on the CPU on the
+# same inputs: the construction and the factor of ATTN_STAGED_FACTOR.  The
+# kernels' blocked sums should be no worse than a sequential fp32 sum.
+LSTM_REF32_FACTOR = 3.0
+
+
+def lstm_rel_fro(x: torch.Tensor, ref64: torch.Tensor) -> float:
+    """||x - ref64||_F / ||ref64||_F, in fp64."""
+    x, ref64 = x.detach().double().cpu(), ref64.detach()
+    return float((x - ref64).norm() / ref64.norm())

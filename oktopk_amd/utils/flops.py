@@ -13,6 +13,8 @@ from typing import Callable, Optional, Tuple
 import torch
 import torch.nn as nn
 
+from ..models.lstm import BatchRNN
+
 
 def _conv2d_flops(m: nn.Conv2d, inp, out) -> int:
     kh, kw = m.kernel_size
@@ -43,6 +45,22 @@ def _lstm_flops(m: nn.LSTM, inp, out) -> int:
         total += dirs * t * b * gates
         isz = m.hidden_size * dirs
     return int(total)
+
+
+def _count_bypassed_lstm(m: BatchRNN, totals) -> list:
+    """With OKTOPK_HIP_LSTM=1 a BatchRNN reads m.rnn's parameters without
+    calling it, so m.rnn's hook does not fire: count the layer from the
+    BatchRNN's own hook whenever that happened (the two see the same
+    [T, N, F] input)."""
+    fired = []
+
+    def after(mod, inp, out):
+        if not fired:
+            totals["flops"] += _lstm_flops(mod.rnn, inp, out)
+        fired.clear()
+
+    return [m.rnn.register_forward_hook(lambda *a: fired.append(1)),
+            m.register_forward_hook(after)]
 
 
 def _elemwise(m, inp, out) -> int:
@@ -103,6 +121,8 @@ def get_model_complexity_info(
                     break
         if fn is not None:
             handles.append(m.register_forward_hook(make_hook(fn)))
+        if isinstance(m, BatchRNN):
+            handles.extend(_count_bypassed_lstm(m, totals))
 
     model.eval()
     with torch.no_grad():

@@ -158,6 +158,51 @@ def residual_ln_rows():
     return rows
 
 
+def lstm_rows():
+    """One 800-wide layer of the lstman4 recipe, T = 101, forward + backward
+    (output gradient given, all five parameter / input gradients taken):
+    nn.LSTM (MIOpen) against ops.hip_lstm.lstm_layer, and lstm_layer's two
+    time loops on their own.  Eager rows carry the host's launch cost, graph
+    rows do not; nn.LSTM has eager rows only, because MIOpen's RNN calls
+    hipBLASLt in a way a capturing stream refuses (error 900).  GB/s counts
+    the W_hh reads alone: 4H * H * 4 bytes per step and pass, served from
+    the last-level cache."""
+    from oktopk_amd.ops.hip_lstm import lstm_layer
+
+    T, Hd = 101, 800
+    rnn = torch.nn.LSTM(Hd, Hd).cuda()
+    params = [rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0]
+    w_hh = rnn.weight_hh_l0.detach()
+    w_hh_t = w_hh.t().contiguous()
+    step_bytes = 4 * Hd * Hd * 4
+
+    def report(name, sec, passes):
+        print(f"{name:44s} {sec * 1000:9.4f} "
+              f"{passes * T * step_bytes / GB / sec:8.0f}", flush=True)
+
+    print(f"{'op':44s} {'ms':>9s} {'GB/s':>8s}")
+    for n in (2, 16):
+        x = torch.randn(T, n, Hd, device="cuda", requires_grad=True)
+        gy = torch.randn(T, n, Hd, device="cuda")
+        gx = torch.randn(T, n, 4 * Hd, device="cuda")
+        act = gx.clone()
+        y, c = H.lstm_fwd(act, w_hh, False)
+
+        def torch_layer():
+            torch.autograd.grad(rnn(x)[0], [x] + params, gy)
+
+        def hip_layer():
+            torch.autograd.grad(lstm_layer(x, *params), [x] + params, gy)
+
+        report(f"nn.LSTM fwd+bwd N={n} (eager)", timeit(torch_layer), 2)
+        report(f"lstm_layer fwd+bwd N={n} (eager)", timeit(hip_layer), 2)
+        report(f"lstm_fwd loop N={n} (graph)",
+               timeit_graph(lambda: H.lstm_fwd(act.copy_(gx), w_hh, False), reps=3), 1)
+        report(f"lstm_bwd loop N={n} (graph)",
+               timeit_graph(lambda: H.lstm_bwd(gy, act, c, y, w_hh_t, False), reps=3), 1)
+        report(f"lstm_layer fwd+bwd N={n} (graph)", timeit_graph(hip_layer, reps=3), 2)
+
+
 def time_both(fn, iters, warmup=5):
     """(device us, host wall us) per call over one window of `iters` calls.
     Wall: host clock around the window, ending in a device synchronise.
@@ -698,7 +743,7 @@ def main():
                          "row, default 15, for --only gauss, topk, "
                          "round2 and reduce)")
     ap.add_argument("--only", default="",
-                    choices=["", "colsum", "deferred", "residual_ln", "wire", "gauss", "sparse_step",
+                    choices=["", "colsum", "deferred", "residual_ln", "lstm", "wire", "gauss", "sparse_step",
                              "topk", "round2", "reduce", "flat_sgd"],
                     help="run just one group of rows")
     args = ap.parse_args()
@@ -717,6 +762,9 @@ def main():
         return
     if args.only == "residual_ln":
         print_rows(residual_ln_rows())
+        return
+    if args.only == "lstm":
+        lstm_rows()
         return
     if args.only == "wire":
         wire_rows(args.iters or 1000)
