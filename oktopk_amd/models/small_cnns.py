@@ -8,6 +8,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops.hip_lstm import (hip_lstm_enabled, hip_lstm_stack_available,
+                            lstm_stack)
+
 
 class AlexNet(nn.Module):
     """CIFAR-sized AlexNet."""
@@ -154,7 +157,12 @@ class PTBLSTM(nn.Module):
 
     def forward(self, x, hidden=None):
         emb = self.drop(self.encoder(x))
-        out, hidden = self.rnn(emb, hidden)
+        if hip_lstm_enabled() and hip_lstm_stack_available(emb, self.rnn):
+            # ops/hip_lstm.py's kernels (OKTOPK_HIP_LSTM=1), read from
+            # self.rnn's own parameters
+            out, hidden = lstm_stack(emb, self.rnn, hidden)
+        else:
+            out, hidden = self.rnn(emb, hidden)
         out = self.drop(out)
         return self.decoder(out), hidden
 

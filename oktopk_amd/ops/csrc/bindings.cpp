@@ -141,11 +141,14 @@ void launch_rm_heads(const int32_t*, const float*, int, int, int, int64_t,
                      int64_t, float, int*, const int*, int32_t*, float*, int,
                      hipStream_t);
 // fused LSTM recurrent step (lstm_cell.hip)
-void launch_lstm_fwd(float* gx, const float* w_hh, float* y, float* c, int T,
-                     int N, int H, int reverse, hipStream_t);
-void launch_lstm_bwd(const float* gy, const float* act, const float* c,
-                     const float* w_hh_t, float* dc_carry, float* dgates, int T,
-                     int N, int H, int reverse, hipStream_t);
+void launch_lstm_fwd(float* gx, const float* w_hh, const float* h0,
+                     const float* c0, float* y, float* c, int T, int N, int H,
+                     int reverse, int batch_tiles, hipStream_t);
+void launch_lstm_bwd(const float* gy, const float* g_hn, const float* g_cn,
+                     const float* act, const float* c, const float* c0,
+                     const float* w_hh_t, float* dc_carry, float* dgates,
+                     float* dh0, int T, int N, int H, int reverse,
+                     int batch_tiles, hipStream_t);
 }
 
 namespace {
@@ -1595,11 +1598,32 @@ static void check_lstm_3d(const torch::Tensor& t, int64_t T, int64_t N,
                 name, " must be [", T, ", ", N, ", ", last, "]");
 }
 
+// An optional [N, H] state tensor: its pointer, nullptr when absent.
+static const float* lstm_state_ptr(const c10::optional<torch::Tensor>& t,
+                                   int64_t N, int64_t H,
+                                   const torch::Tensor& like, const char* name) {
+    if (!t.has_value()) return nullptr;
+    check_f32_1d(*t, name);
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == N && t->size(1) == H, name,
+                " must be [", N, ", ", H, "]");
+    TORCH_CHECK(t->device() == like.device(), name, ": device mismatch");
+    return t->data_ptr<float>();
+}
+
+static void check_batch_tiles(int64_t batch_tiles) {
+    TORCH_CHECK(batch_tiles >= 0 && batch_tiles <= 2,
+                "batch_tiles must be 0 (auto), 1 or 2");
+}
+
 static std::vector<torch::Tensor> lstm_fwd(torch::Tensor gx, torch::Tensor w_hh,
-                                           bool reverse) {
+                                           bool reverse,
+                                           c10::optional<torch::Tensor> h0,
+                                           c10::optional<torch::Tensor> c0,
+                                           int64_t batch_tiles) {
     // gx [T, N, 4H]: x @ W_ih^T + b_ih + b_hh in, the activations (i, f, g, o)
-    // out, in place.  Zero initial state.  Returns {y, c}, both [T, N, H].
-    // T launches on the current stream, nothing read back: capturable.
+    // out, in place.  h0 / c0 [N, H]: the initial state, zeros when absent.
+    // Returns {y, c}, both [T, N, H].  T launches on the current stream,
+    // nothing read back: capturable.
     check_f32_1d(gx, "gx");
     check_f32_1d(w_hh, "w_hh");
     TORCH_CHECK(gx.dim() == 3 && w_hh.dim() == 2, "gx [T, N, 4H], w_hh [4H, H]");
@@ -1612,21 +1636,30 @@ static std::vector<torch::Tensor> lstm_fwd(torch::Tensor gx, torch::Tensor w_hh,
     TORCH_CHECK(N * 4 * H < ((int64_t)1 << 31) && N <= 16 * 65535 &&
                     T < ((int64_t)1 << 31),
                 "lstm_fwd: shape too large");
+    check_batch_tiles(batch_tiles);
+    const float* h0p = lstm_state_ptr(h0, N, H, gx, "h0");
+    const float* c0p = lstm_state_ptr(c0, N, H, gx, "c0");
     const at::cuda::CUDAGuard guard(gx.device());
     auto y = torch::empty({T, N, H}, gx.options());
     auto c = torch::empty({T, N, H}, gx.options());
-    launch_lstm_fwd(gx.data_ptr<float>(), w_hh.data_ptr<float>(),
+    launch_lstm_fwd(gx.data_ptr<float>(), w_hh.data_ptr<float>(), h0p, c0p,
                     y.data_ptr<float>(), c.data_ptr<float>(), (int)T, (int)N,
-                    (int)H, reverse ? 1 : 0, cur_stream());
+                    (int)H, reverse ? 1 : 0, (int)batch_tiles, cur_stream());
     return {y, c};
 }
 
-static torch::Tensor lstm_bwd(torch::Tensor gy, torch::Tensor act,
-                              torch::Tensor c, torch::Tensor y,
-                              torch::Tensor w_hh_t, bool reverse) {
+static py::object lstm_bwd(torch::Tensor gy, torch::Tensor act, torch::Tensor c,
+                           torch::Tensor y, torch::Tensor w_hh_t, bool reverse,
+                           c10::optional<torch::Tensor> g_hn,
+                           c10::optional<torch::Tensor> g_cn,
+                           c10::optional<torch::Tensor> c0, bool need_dh0,
+                           int64_t batch_tiles) {
     // dgates [T, N, 4H]: the gradient at the pre-activation gates, from gy
     // (the gradient at y), lstm_fwd's activations and c, and W_hh^T [H, 4H].
     // The steps recompute tanh(c_t), so y only fixes the shapes.
+    // g_hn / g_cn [N, H]: gradients at the final state; c0: the initial cell
+    // state lstm_fwd was given; need_dh0: lstm_fwd was given an h0.  With any
+    // of the four the result is (dgates, dh0 or None, dc0), both [N, H].
     TORCH_CHECK(y.dim() == 3, "lstm_bwd: y must be [T, N, H]");
     const int64_t T = y.size(0), N = y.size(1), H = y.size(2);
     TORCH_CHECK(T >= 1 && N >= 1 && H >= 4 && H % 4 == 0,
@@ -1644,15 +1677,24 @@ static torch::Tensor lstm_bwd(torch::Tensor gy, torch::Tensor act,
     TORCH_CHECK(N * 4 * H < ((int64_t)1 << 31) && N <= 16 * 65535 &&
                     T < ((int64_t)1 << 31),
                 "lstm_bwd: shape too large");
+    check_batch_tiles(batch_tiles);
+    const float* g_hnp = lstm_state_ptr(g_hn, N, H, act, "g_hn");
+    const float* g_cnp = lstm_state_ptr(g_cn, N, H, act, "g_cn");
+    const float* c0p = lstm_state_ptr(c0, N, H, act, "c0");
     const at::cuda::CUDAGuard guard(act.device());
     auto dgates = torch::empty_like(act);
     // written by the first step before any step reads it
     auto dc_carry = torch::empty({N, H}, act.options());
-    launch_lstm_bwd(gy.data_ptr<float>(), act.data_ptr<float>(),
-                    c.data_ptr<float>(), w_hh_t.data_ptr<float>(),
-                    dc_carry.data_ptr<float>(), dgates.data_ptr<float>(), (int)T,
-                    (int)N, (int)H, reverse ? 1 : 0, cur_stream());
-    return dgates;
+    torch::Tensor dh0;
+    if (need_dh0) dh0 = torch::empty({N, H}, act.options());
+    launch_lstm_bwd(gy.data_ptr<float>(), g_hnp, g_cnp, act.data_ptr<float>(),
+                    c.data_ptr<float>(), c0p, w_hh_t.data_ptr<float>(),
+                    dc_carry.data_ptr<float>(), dgates.data_ptr<float>(),
+                    need_dh0 ? dh0.data_ptr<float>() : nullptr, (int)T, (int)N,
+                    (int)H, reverse ? 1 : 0, (int)batch_tiles, cur_stream());
+    if (!(need_dh0 || g_hnp || g_cnp || c0p)) return py::cast(dgates);
+    return py::make_tuple(dgates, need_dh0 ? py::cast(dh0) : py::none(),
+                          dc_carry);
 }
 
 static std::vector<torch::Tensor> attn_fwd_fa(torch::Tensor qkv,
@@ -1955,12 +1997,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "gy = gy1 + gy2, LayerNorm input gradient, dropout backward: "
           "{gy, gs, ga}, torch's bits, one launch");
     m.def("lstm_fwd", &lstm_fwd,
-          "fp32 LSTM time loop, zero initial state: gx [T, N, 4H] -> "
-          "activations in place; returns {y, c}; one launch per step",
-          py::arg("gx"), py::arg("w_hh"), py::arg("reverse"));
+          "fp32 LSTM time loop from (h0, c0), zeros when None: gx [T, N, 4H] -> "
+          "activations in place; returns {y, c}; one launch per step; "
+          "batch_tiles per block: 0 auto, 1, 2 (same bits)",
+          py::arg("gx"), py::arg("w_hh"), py::arg("reverse"),
+          py::arg("h0") = py::none(), py::arg("c0") = py::none(),
+          py::arg("batch_tiles") = 0);
     m.def("lstm_bwd", &lstm_bwd,
           "backward of lstm_fwd's time loop: dgates [T, N, 4H]; one launch "
-          "per step",
+          "per step.  With g_hn / g_cn (gradients at the final state), c0 or "
+          "need_dh0: (dgates, dh0 or None, dc0), dh0 from one more launch",
           py::arg("gy"), py::arg("act"), py::arg("c"), py::arg("y"),
-          py::arg("w_hh_t"), py::arg("reverse"));
+          py::arg("w_hh_t"), py::arg("reverse"), py::arg("g_hn") = py::none(),
+          py::arg("g_cn") = py::none(), py::arg("c0") = py::none(),
+          py::arg("need_dh0") = false, py::arg("batch_tiles") = 0);
 }

@@ -1038,24 +1038,27 @@ def attn_lse_bound(lse64: torch.Tensor) -> torch.Tensor:
 
 # -- LSTM layer -----------------------------------------------------------------
 
-def lstm_layer_ref(x, w_ih, w_hh, b_ih, b_hh, reverse: bool = False):
-    """One LSTM direction with zero initial state as a torch loop over time:
-    x [T, N, F] -> y [T, N, H], torch's gate order (i, f, g, o as row blocks
-    of w_ih [4H, F] / w_hh [4H, H]); `reverse` walks time from T-1 to 0.
-    Differentiable, in the dtype it is given: the CPU path of
+def lstm_layer_ref(x, w_ih, w_hh, b_ih, b_hh, reverse: bool = False,
+                   h0=None, c0=None, return_state: bool = False):
+    """One LSTM direction as a torch loop over time, from (h0, c0) [N, H] or
+    a zero state: x [T, N, F] -> y [T, N, H], torch's gate order (i, f, g, o
+    as row blocks of w_ih [4H, F] / w_hh [4H, H]); `reverse` walks time from
+    T-1 to 0.  With return_state: (y, h_n, c_n), the state after the last
+    step.  Differentiable, in the dtype it is given: the CPU path of
     ops.hip_lstm.lstm_layer, its fp32 yardstick and, in fp64, its oracle."""
     T, N, _ = x.shape
     H = w_hh.shape[1]
     gx = (x.reshape(T * N, -1) @ w_ih.t() + (b_ih + b_hh)).view(T, N, 4 * H)
-    h = x.new_zeros(N, H)
-    c = x.new_zeros(N, H)
+    h = x.new_zeros(N, H) if h0 is None else h0
+    c = x.new_zeros(N, H) if c0 is None else c0
     ys = [None] * T
     for t in (range(T - 1, -1, -1) if reverse else range(T)):
         i, f, g, o = (gx[t] + h @ w_hh.t()).chunk(4, dim=1)
         c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
         h = torch.sigmoid(o) * torch.tanh(c)
         ys[t] = h
-    return torch.stack(ys)
+    y = torch.stack(ys)
+    return (y, h, c) if return_state else y
 
 
 # A kernel result passes when its rel_fro against the fp64 oracle, per tensor,

@@ -201,6 +201,55 @@ def lstm_rows():
         report(f"lstm_bwd loop N={n} (graph)",
                timeit_graph(lambda: H.lstm_bwd(gy, act, c, y, w_hh_t, False), reps=3), 1)
         report(f"lstm_layer fwd+bwd N={n} (graph)", timeit_graph(hip_layer, reps=3), 2)
+    lstm_stack_rows()
+
+
+def lstm_stack_rows():
+    """The PTB word LM's two 1500-wide layers, T = 35, N = 20, forward +
+    backward with an initial state and gradients at the final one: nn.LSTM
+    (MIOpen, eager only) against ops.hip_lstm.lstm_stack, and one layer's two
+    time loops with one batch tile per block against two (batch_tiles).  GB/s
+    counts one W_hh read per step, pass and layer: what the pair moves, half
+    of what single tiles do at 16 < N <= 32."""
+    from oktopk_amd.ops.hip_lstm import lstm_stack
+
+    T, n, Hd, L = 35, 20, 1500, 2
+    rnn = torch.nn.LSTM(Hd, Hd, num_layers=L).cuda()
+    params = list(rnn.parameters())
+    w_hh = rnn.weight_hh_l0.detach()
+    w_hh_t = w_hh.t().contiguous()
+    step_bytes = 4 * Hd * Hd * 4
+
+    def report(name, sec, passes):
+        print(f"{name:44s} {sec * 1000:9.4f} "
+              f"{passes * T * step_bytes / GB / sec:8.0f}", flush=True)
+
+    x = torch.randn(T, n, Hd, device="cuda", requires_grad=True)
+    hidden = tuple(torch.randn(L, n, Hd, device="cuda", requires_grad=True)
+                   for _ in range(2))
+    gouts = [torch.randn(T, n, Hd, device="cuda")] + [torch.randn_like(h) for h in hidden]
+    gy, g_hn, g_cn = gouts[0], gouts[1][0], gouts[2][0]
+    h0, c0 = hidden[0][0].detach(), hidden[1][0].detach()
+    gx = torch.randn(T, n, 4 * Hd, device="cuda")
+    act = gx.clone()
+    y, c = H.lstm_fwd(act, w_hh, False, h0, c0)
+
+    def layers(fn):
+        out, (h_n, c_n) = fn(x, hidden)
+        torch.autograd.grad([out, h_n, c_n], [x, *hidden] + params, gouts)
+
+    hip_stack = lambda: layers(lambda a, hid: lstm_stack(a, rnn, hid))
+    report(f"nn.LSTM x{L} fwd+bwd H={Hd} N={n} (eager)", timeit(lambda: layers(rnn)), 2 * L)
+    report(f"lstm_stack x{L} fwd+bwd H={Hd} N={n} (eager)", timeit(hip_stack), 2 * L)
+    report(f"lstm_stack x{L} fwd+bwd H={Hd} N={n} (graph)",
+           timeit_graph(hip_stack, reps=3), 2 * L)
+    for tiles in (1, 2):
+        report(f"lstm_fwd loop H={Hd} N={n} tiles={tiles} (graph)",
+               timeit_graph(lambda: H.lstm_fwd(act.copy_(gx), w_hh, False, h0, c0, tiles),
+                            reps=3), 1)
+        report(f"lstm_bwd loop H={Hd} N={n} tiles={tiles} (graph)",
+               timeit_graph(lambda: H.lstm_bwd(gy, act, c, y, w_hh_t, False, g_hn, g_cn,
+                                               c0, True, tiles), reps=3), 1)
 
 
 def time_both(fn, iters, warmup=5):
