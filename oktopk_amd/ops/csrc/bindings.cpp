@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "colsum_exact_config.h"
+#include "ctc_loss.h"
 #include "grad_batch.h"
 
 // launchers from kernels.hip
@@ -149,6 +150,10 @@ void launch_lstm_bwd(const float* gy, const float* g_hn, const float* g_cn,
                      const float* w_hh_t, float* dc_carry, float* dgates,
                      float* dh0, int T, int N, int H, int reverse,
                      int batch_tiles, hipStream_t);
+// fused CTC loss (ctc_loss.hip)
+void launch_ctc_loss(const CtcArgs* a, hipStream_t);
+void launch_ctc_scale_grad(const float* g, const float* gout, float* out,
+                           long long total, int N, int C, hipStream_t);
 }
 
 namespace {
@@ -1697,6 +1702,96 @@ static py::object lstm_bwd(torch::Tensor gy, torch::Tensor act, torch::Tensor c,
                           dc_carry);
 }
 
+// -- fused CTC loss (ctc_loss.hip) ---------------------------------------------
+
+static bool ctc_int_tensor(const torch::Tensor& t) {
+    return t.scalar_type() == torch::kInt32 || t.scalar_type() == torch::kInt64;
+}
+
+static std::vector<torch::Tensor> ctc_loss_fwd(torch::Tensor logits,
+                                               torch::Tensor targets,
+                                               torch::Tensor input_lengths,
+                                               torch::Tensor target_lengths,
+                                               int64_t blank, bool zero_infinity,
+                                               bool want_grad) {
+    // logits [T, N, C] raw; targets padded [N, Lmax] or 1-D concatenated;
+    // lengths [N]; all integer tensors int32 or int64 on logits' device.
+    // Returns {nll [N], grad [T, N, C]} (grad: the gradient of sum(nll) at the
+    // raw logits; an empty tensor without want_grad).  One launch on the
+    // current stream, nothing read back: capturable.
+    check_f32_1d(logits, "logits");
+    TORCH_CHECK(logits.dim() == 3, "ctc_loss_fwd: logits must be [T, N, C]");
+    const int64_t T = logits.size(0), N = logits.size(1), C = logits.size(2);
+    TORCH_CHECK(T >= 1 && N >= 1 && C >= 1, "ctc_loss_fwd: needs T, N, C >= 1");
+    TORCH_CHECK(T < ((int64_t)1 << 31) && N < ((int64_t)1 << 31) &&
+                    C < ((int64_t)1 << 31),
+                "ctc_loss_fwd: shape too large");
+    TORCH_CHECK(blank >= 0 && blank < C, "ctc_loss_fwd: blank must be in [0, C)");
+    for (auto* p : {&targets, &input_lengths, &target_lengths}) {
+        TORCH_CHECK(ctc_int_tensor(*p), "ctc_loss_fwd: lengths and targets must "
+                                        "be int32 or int64");
+        TORCH_CHECK(p->device() == logits.device(), "ctc_loss_fwd: device mismatch");
+        TORCH_CHECK(p->is_contiguous(), "ctc_loss_fwd: lengths and targets must "
+                                        "be contiguous");
+    }
+    TORCH_CHECK(input_lengths.dim() == 1 && input_lengths.size(0) == N &&
+                    target_lengths.dim() == 1 && target_lengths.size(0) == N,
+                "ctc_loss_fwd: lengths must be [N]");
+    TORCH_CHECK(targets.dim() == 1 || (targets.dim() == 2 && targets.size(0) == N),
+                "ctc_loss_fwd: targets must be [N, Lmax] or 1-D");
+    const bool padded = targets.dim() == 2;
+    TORCH_CHECK(!padded || targets.size(1) <= CTC_MAX_L,
+                "ctc_loss_fwd: padded targets wider than ", CTC_MAX_L);
+    const int64_t Sst = 2 * (padded ? targets.size(1) : (int64_t)CTC_MAX_L) + 1;
+
+    const at::cuda::CUDAGuard guard(logits.device());
+    auto nll = torch::empty({N}, logits.options());
+    torch::Tensor grad, ws;
+    if (want_grad) grad = torch::empty_like(logits);
+    const size_t lat = ctc_lattice_floats(T, Sst);
+    if (lat * sizeof(float) > CTC_LDS_BUDGET)
+        ws = torch::empty({N, (int64_t)lat}, logits.options());
+
+    CtcArgs a;
+    a.logits = logits.data_ptr<float>();
+    a.targets = targets.data_ptr();
+    a.in_len = input_lengths.data_ptr();
+    a.tgt_len = target_lengths.data_ptr();
+    a.nll = nll.data_ptr<float>();
+    a.grad = want_grad ? grad.data_ptr<float>() : nullptr;
+    a.ws = ws.defined() ? ws.data_ptr<float>() : nullptr;
+    a.tgt_stride = padded ? targets.size(1) : -1;
+    a.tgt_numel = targets.numel();
+    a.T = (int)T;
+    a.N = (int)N;
+    a.C = (int)C;
+    a.blank = (int)blank;
+    a.Sst = (int)Sst;
+    a.targets_i64 = targets.scalar_type() == torch::kInt64;
+    a.in_len_i64 = input_lengths.scalar_type() == torch::kInt64;
+    a.tgt_len_i64 = target_lengths.scalar_type() == torch::kInt64;
+    a.zero_infinity = zero_infinity ? 1 : 0;
+    launch_ctc_loss(&a, cur_stream());
+    if (!want_grad) grad = torch::empty({0}, logits.options());
+    return {nll, grad};
+}
+
+static torch::Tensor ctc_scale_grad(torch::Tensor grad, torch::Tensor gout) {
+    // grad [T, N, C] * gout [N], broadcast over t and c, into a new tensor.
+    check_f32_1d(grad, "grad");
+    check_f32_1d(gout, "gout");
+    TORCH_CHECK(grad.dim() == 3 && gout.dim() == 1 &&
+                    gout.size(0) == grad.size(1) && grad.numel() >= 1,
+                "ctc_scale_grad: grad [T, N, C] and gout [N]");
+    TORCH_CHECK(gout.device() == grad.device(), "ctc_scale_grad: device mismatch");
+    const at::cuda::CUDAGuard guard(grad.device());
+    auto out = torch::empty_like(grad);
+    launch_ctc_scale_grad(grad.data_ptr<float>(), gout.data_ptr<float>(),
+                          out.data_ptr<float>(), grad.numel(),
+                          (int)grad.size(1), (int)grad.size(2), cur_stream());
+    return out;
+}
+
 static std::vector<torch::Tensor> attn_fwd_fa(torch::Tensor qkv,
                                               torch::Tensor mask,
                                               int64_t num_heads,
@@ -2011,4 +2106,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("w_hh_t"), py::arg("reverse"), py::arg("g_hn") = py::none(),
           py::arg("g_cn") = py::none(), py::arg("c0") = py::none(),
           py::arg("need_dh0") = false, py::arg("batch_tiles") = 0);
+    m.def("ctc_loss_fwd", &ctc_loss_fwd,
+          "CTC negative log-likelihood [N] from raw logits [T, N, C] and, with "
+          "want_grad, its gradient at the logits: {nll, grad}; one launch, no "
+          "host sync",
+          py::arg("logits"), py::arg("targets"), py::arg("input_lengths"),
+          py::arg("target_lengths"), py::arg("blank"),
+          py::arg("zero_infinity"), py::arg("want_grad"));
+    m.def("ctc_scale_grad", &ctc_scale_grad,
+          "grad [T, N, C] * gout [N] per utterance, one launch");
+    m.def("ctc_lds_budget", []() { return (int64_t)CTC_LDS_BUDGET; },
+          "bytes of LDS the CTC lattices may take: T (2 Sst + 2) floats");
+    m.def("ctc_max_target_length", []() { return (int64_t)CTC_MAX_L; });
 }

@@ -1072,3 +1072,26 @@ def lstm_rel_fro(x: torch.Tensor, ref64: torch.Tensor) -> float:
     """||x - ref64||_F / ||ref64||_F, in fp64."""
     x, ref64 = x.detach().double().cpu(), ref64.detach()
     return float((x - ref64).norm() / ref64.norm())
+
+
+# -- CTC loss (ops/hip_ctc.py) --------------------------------------------------
+
+def ctc_loss_ref(logits, targets, input_lengths, target_lengths, blank: int = 0,
+                 reduction: str = "mean", zero_infinity: bool = False):
+    """F.ctc_loss over F.log_softmax(logits, -1), in the dtype of logits
+    [T, N, C]; input lengths clamped to T as the kernel clamps them.  The CPU
+    path of hip_ctc.ctc_loss and, in fp64, the oracle of its tests."""
+    import torch.nn.functional as F
+
+    return F.ctc_loss(F.log_softmax(logits, -1), targets,
+                      torch.clamp(input_lengths, max=logits.size(0)),
+                      target_lengths, blank=blank, reduction=reduction,
+                      zero_infinity=zero_infinity)
+
+
+# The rule of LSTM_REF32_FACTOR for the CTC kernel: its gradient's rel_fro
+# against the fp64 oracle is at most this many times that of ctc_loss_ref in
+# fp32 on the CPU on the same inputs.  For the loss, a handful of scalars, the
+# yardstick's error is floored at one fp32 epsilon (CTC_LOSS_FLOOR).
+CTC_REF32_FACTOR = 3.0
+CTC_LOSS_FLOOR = 2.0 ** -23

@@ -17,6 +17,7 @@ import torch
 from . import models
 from .comm import Comm
 from .config import EngineConfig
+from .ops import hip_ctc
 from .optimizer import DistributedOptimizer, FlatBertAdam, FlatSGD
 
 logger = logging.getLogger("oktopk_amd")
@@ -250,6 +251,12 @@ class Trainer:
             )
         if self.model_name == "lstman4":
             logits = self.model(b.x)  # (T, N, C)
+            if hip_ctc.hip_ctc_enabled():
+                # fused HIP loss, no host staging: capturable (ops/hip_ctc.py)
+                lf = logits.float()
+                if hip_ctc.hip_ctc_available(lf, b.target, b.in_len, b.tgt_len):
+                    return hip_ctc.ctc_loss(lf, b.target, b.in_len, b.tgt_len,
+                                            blank=0, zero_infinity=True)
             logp = torch.nn.functional.log_softmax(logits, dim=-1)
             t = logp.size(0)
             in_len = torch.clamp(b.in_len, max=t)
@@ -282,7 +289,9 @@ class Trainer:
     def capture_graph(self) -> bool:
         """Capture fwd+bwd into a hipGraph (call after a few eager warmup
         steps).  Returns False (and stays eager) when the model is not
-        capturable (e.g. CTC loss) or no GPU is present."""
+        capturable or no GPU is present: lstman4 with torch's ctc_loss, which
+        stages lengths through the host, or with MIOpen's RNN; it captures
+        with OKTOPK_HIP_LSTM=1 and OKTOPK_HIP_CTC=1."""
         if self.device.type != "cuda" or self.nsteps_update != 1:
             return False
         if getattr(self.opt, "local", False):

@@ -29,6 +29,7 @@ setup(
                 "oktopk_amd/ops/csrc/residual_ln.hip",
                 "oktopk_amd/ops/csrc/attention_fa.hip",
                 "oktopk_amd/ops/csrc/lstm_cell.hip",
+                "oktopk_amd/ops/csrc/ctc_loss.hip",
             ],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],

@@ -204,6 +204,40 @@ def lstm_rows():
     lstm_stack_rows()
 
 
+def ctc_rows():
+    """The lstman4 recipe's loss, T = 101, C = 29, L = 20, forward + backward
+    to the logits: F.log_softmax + F.ctc_loss (eager only: torch's GPU
+    ctc_loss stages lengths through the host, which a capturing stream
+    refuses) against ops.hip_ctc.ctc_loss, and the kernel launch alone."""
+    import torch.nn.functional as F
+
+    from oktopk_amd.ops.hip_ctc import ctc_loss
+
+    T, C, L = 101, 29, 20
+    print(f"{'op':44s} {'us':>9s}")
+    report = lambda name, sec: print(f"{name:44s} {sec * 1e6:9.1f}", flush=True)
+    for n in (2, 16):
+        x = torch.randn(T, n, C, device="cuda", requires_grad=True)
+        tgt = torch.randint(1, C, (n, L), device="cuda")
+        il = torch.full((n,), T, dtype=torch.int32, device="cuda")
+        tl = torch.full((n,), L, dtype=torch.int32, device="cuda")
+
+        def torch_loss():
+            torch.autograd.grad(F.ctc_loss(F.log_softmax(x, -1), tgt, il, tl,
+                                           zero_infinity=True), x)
+
+        def hip_loss():
+            torch.autograd.grad(ctc_loss(x, tgt, il, tl, zero_infinity=True), x)
+
+        xd = x.detach()
+        report(f"log_softmax + ctc_loss fwd+bwd N={n} (eager)", timeit(torch_loss))
+        report(f"hip_ctc.ctc_loss fwd+bwd N={n} (eager)", timeit(hip_loss))
+        report(f"hip_ctc.ctc_loss fwd+bwd N={n} (graph)", timeit_graph(hip_loss, reps=20))
+        report(f"ctc_loss_fwd launch N={n} (graph)",
+               timeit_graph(lambda: H.ctc_loss_fwd(xd, tgt, il, tl, 0, True, True),
+                            reps=20))
+
+
 def lstm_stack_rows():
     """The PTB word LM's two 1500-wide layers, T = 35, N = 20, forward +
     backward with an initial state and gradients at the final one: nn.LSTM
@@ -792,7 +826,7 @@ def main():
                          "row, default 15, for --only gauss, topk, "
                          "round2 and reduce)")
     ap.add_argument("--only", default="",
-                    choices=["", "colsum", "deferred", "residual_ln", "lstm", "wire", "gauss", "sparse_step",
+                    choices=["", "colsum", "deferred", "residual_ln", "lstm", "ctc", "wire", "gauss", "sparse_step",
                              "topk", "round2", "reduce", "flat_sgd"],
                     help="run just one group of rows")
     args = ap.parse_args()
@@ -814,6 +848,9 @@ def main():
         return
     if args.only == "lstm":
         lstm_rows()
+        return
+    if args.only == "ctc":
+        ctc_rows()
         return
     if args.only == "wire":
         wire_rows(args.iters or 1000)
