@@ -227,12 +227,14 @@ class BertForPreTraining(nn.Module):
         nsp_logits = self.nsp(pooled)
         if masked_lm_labels is None:
             return logits, nsp_logits
-        mlm_loss = F.cross_entropy(
+        from ..ops.hip_ce import cross_entropy  # F.cross_entropy unless OKTOPK_HIP_CE=1
+
+        mlm_loss = cross_entropy(
             logits.view(-1, logits.size(-1)), masked_lm_labels.view(-1), ignore_index=-1
         )
         loss = mlm_loss
         if next_sentence_label is not None:
-            loss = loss + F.cross_entropy(nsp_logits.view(-1, 2), next_sentence_label.view(-1))
+            loss = loss + cross_entropy(nsp_logits.view(-1, 2), next_sentence_label.view(-1))
         return loss
 
 

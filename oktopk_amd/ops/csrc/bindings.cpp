@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "colsum_exact_config.h"
+#include "cross_entropy.h"
 #include "ctc_loss.h"
 #include "grad_batch.h"
 
@@ -154,6 +155,10 @@ void launch_lstm_bwd(const float* gy, const float* g_hn, const float* g_cn,
 void launch_ctc_loss(const CtcArgs* a, hipStream_t);
 void launch_ctc_scale_grad(const float* g, const float* gout, float* out,
                            long long total, int N, int C, hipStream_t);
+// fused cross-entropy (cross_entropy.hip)
+void launch_ce_fwd(const CeArgs* a, hipStream_t);
+void launch_ce_finalize(const CeArgs* a, int reduction, float* out, hipStream_t);
+void launch_ce_bwd(const CeBwdArgs* a, hipStream_t);
 }
 
 namespace {
@@ -1792,6 +1797,113 @@ static torch::Tensor ctc_scale_grad(torch::Tensor grad, torch::Tensor gout) {
     return out;
 }
 
+// -- fused cross-entropy (cross_entropy.hip) -----------------------------------
+
+static void ce_check(const torch::Tensor& logits, const torch::Tensor& target,
+                     const char* fn) {
+    TORCH_CHECK(logits.is_cuda(), fn, ": logits must be a GPU tensor");
+    TORCH_CHECK(logits.scalar_type() == torch::kFloat32 ||
+                    logits.scalar_type() == torch::kBFloat16,
+                fn, ": logits must be fp32 or bf16");
+    TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), fn,
+                ": logits must be contiguous [R, C]");
+    const int64_t R = logits.size(0), C = logits.size(1);
+    TORCH_CHECK(R >= 1 && C >= 1, fn, ": needs R, C >= 1");
+    TORCH_CHECK(R * C < ((int64_t)1 << 31) &&
+                    R * C * (int64_t)logits.element_size() < ((int64_t)1 << 31),
+                fn, ": shape too large");
+    TORCH_CHECK(ctc_int_tensor(target), fn, ": target must be int32 or int64");
+    TORCH_CHECK(target.device() == logits.device(), fn, ": device mismatch");
+    TORCH_CHECK(target.dim() == 1 && target.size(0) == R && target.is_contiguous(),
+                fn, ": target must be contiguous [R]");
+}
+
+static std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor target,
+                                         int64_t ignore_index, int64_t reduction) {
+    // logits [R, C] fp32 or bf16; target [R] int32 or int64; reduction 0 none,
+    // 1 mean, 2 sum.  Returns {loss (fp32: [R], or 0-dim), stats [2, R] (row
+    // maximum, log of the row's sum of exponentials), factor [1] (what the
+    // reduction multiplies every row's gradient by; empty for none)}.  Two
+    // launches on the current stream (one for none), nothing read back.
+    ce_check(logits, target, "ce_fwd");
+    TORCH_CHECK(reduction >= 0 && reduction <= 2, "ce_fwd: reduction must be 0 "
+                                                  "(none), 1 (mean) or 2 (sum)");
+    const int64_t R = logits.size(0), C = logits.size(1);
+    const at::cuda::CUDAGuard guard(logits.device());
+    const auto f32 = logits.options().dtype(torch::kFloat32);
+    auto row_loss = torch::empty({R}, f32);
+    auto stats = torch::empty({2, R}, f32);
+
+    CeArgs a;
+    a.logits = logits.data_ptr();
+    a.target = target.data_ptr();
+    a.row_loss = row_loss.data_ptr<float>();
+    a.stats = stats.data_ptr<float>();
+    a.ignore_index = ignore_index;
+    a.R = R;
+    a.C = (int)C;
+    a.is_bf16 = logits.scalar_type() == torch::kBFloat16;
+    a.target_i64 = target.scalar_type() == torch::kInt64;
+    launch_ce_fwd(&a, cur_stream());
+    if (reduction == 0) return {row_loss, stats, torch::empty({0}, f32)};
+    auto out = torch::empty({2}, f32);
+    launch_ce_finalize(&a, (int)reduction, out.data_ptr<float>(), cur_stream());
+    return {out.select(0, 0), stats, out.narrow(0, 1, 1)};
+}
+
+static torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor target,
+                            torch::Tensor stats, torch::Tensor factor,
+                            torch::Tensor gout, int64_t ignore_index) {
+    // The gradient at the logits, in their dtype, from ce_fwd's stats and
+    // factor and the upstream gradient gout (fp32: [R] when factor is empty,
+    // else one element).  One launch, nothing read back.
+    ce_check(logits, target, "ce_bwd");
+    const int64_t R = logits.size(0), C = logits.size(1);
+    check_f32_1d(stats, "stats");
+    check_f32_1d(factor, "factor");
+    check_f32_1d(gout, "gout");
+    TORCH_CHECK(stats.dim() == 2 && stats.size(0) == 2 && stats.size(1) == R,
+                "ce_bwd: stats must be [2, R]");
+    const bool per_row = factor.numel() == 0;
+    TORCH_CHECK(per_row || factor.numel() == 1, "ce_bwd: factor must hold one "
+                                                "element or none");
+    TORCH_CHECK(gout.numel() == (per_row ? R : 1),
+                "ce_bwd: gout must be [R] without a reduction, else one element");
+    TORCH_CHECK(stats.device() == logits.device() &&
+                    factor.device() == logits.device() &&
+                    gout.device() == logits.device(),
+                "ce_bwd: device mismatch");
+
+    const at::cuda::CUDAGuard guard(logits.device());
+    // grad sits at the logits' offset from a 16-byte boundary (a view of a
+    // larger buffer may start anywhere), so a row's head, vectors and tail
+    // are the same elements on both sides
+    const int64_t es = logits.element_size();
+    const int64_t off =
+        (int64_t)(reinterpret_cast<uintptr_t>(logits.data_ptr()) & 15u) / es;
+    auto buf = torch::empty({R * C + off}, logits.options());
+    auto grad = buf.narrow(0, off, R * C).view({R, C});
+    TORCH_CHECK(((reinterpret_cast<uintptr_t>(grad.data_ptr()) ^
+                  reinterpret_cast<uintptr_t>(logits.data_ptr())) & 15u) == 0,
+                "ce_bwd: gradient buffer not aligned like the logits");
+
+    CeBwdArgs a;
+    a.logits = logits.data_ptr();
+    a.target = target.data_ptr();
+    a.stats = stats.data_ptr<float>();
+    a.gout = gout.data_ptr<float>();
+    a.factor = per_row ? nullptr : factor.data_ptr<float>();
+    a.grad = grad.data_ptr();
+    a.ignore_index = ignore_index;
+    a.R = R;
+    a.C = (int)C;
+    a.is_bf16 = logits.scalar_type() == torch::kBFloat16;
+    a.target_i64 = target.scalar_type() == torch::kInt64;
+    a.gout_per_row = per_row ? 1 : 0;
+    launch_ce_bwd(&a, cur_stream());
+    return grad;
+}
+
 static std::vector<torch::Tensor> attn_fwd_fa(torch::Tensor qkv,
                                               torch::Tensor mask,
                                               int64_t num_heads,
@@ -2118,4 +2230,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("ctc_lds_budget", []() { return (int64_t)CTC_LDS_BUDGET; },
           "bytes of LDS the CTC lattices may take: T (2 Sst + 2) floats");
     m.def("ctc_max_target_length", []() { return (int64_t)CTC_MAX_L; });
+    m.def("ce_fwd", &ce_fwd,
+          "cross-entropy of raw logits [R, C] (fp32 / bf16) against class "
+          "targets [R]: {loss fp32, stats [2, R], factor}; reduction 0 none, "
+          "1 mean, 2 sum; no host sync",
+          py::arg("logits"), py::arg("target"), py::arg("ignore_index"),
+          py::arg("reduction"));
+    m.def("ce_bwd", &ce_bwd,
+          "gradient of ce_fwd at the logits, in their dtype; one launch",
+          py::arg("logits"), py::arg("target"), py::arg("stats"),
+          py::arg("factor"), py::arg("gout"), py::arg("ignore_index"));
 }

@@ -1095,3 +1095,20 @@ def ctc_loss_ref(logits, targets, input_lengths, target_lengths, blank: int = 0,
 # yardstick's error is floored at one fp32 epsilon (CTC_LOSS_FLOOR).
 CTC_REF32_FACTOR = 3.0
 CTC_LOSS_FLOOR = 2.0 ** -23
+
+
+# -- cross-entropy (ops/hip_ce.py) ----------------------------------------------
+
+def cross_entropy_ref(logits, target, ignore_index: int = -100,
+                      reduction: str = "mean"):
+    """F.cross_entropy in the dtype of logits [R, C]: in fp64 the oracle of
+    the cross-entropy kernels' tests, in fp32 their yardstick."""
+    import torch.nn.functional as F
+
+    return F.cross_entropy(logits, target.long(), ignore_index=ignore_index,
+                           reduction=reduction)
+
+
+# The CTC rule and its constants, for the cross-entropy kernels.
+CE_REF32_FACTOR = 3.0
+CE_LOSS_FLOOR = 2.0 ** -23

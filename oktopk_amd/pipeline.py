@@ -96,6 +96,8 @@ class BertEndStage(nn.Module):
     def forward(self, hidden, attention_mask, masked_lm_labels, next_sentence_label):
         import torch.nn.functional as F
 
+        from .ops.hip_ce import cross_entropy  # F.cross_entropy unless OKTOPK_HIP_CE=1
+
         wdt = hidden.dtype
         mask = (1.0 - attention_mask[:, None, None, :].to(wdt)) * -10000.0
         x = hidden
@@ -104,13 +106,13 @@ class BertEndStage(nn.Module):
         pooled = torch.tanh(self.pooler(x[:, 0]))
         h = self.transform_ln(F.gelu(self.transform(x)))
         logits = self.decoder(h)
-        loss = F.cross_entropy(
+        loss = cross_entropy(
             logits.view(-1, logits.size(-1)).float(),
             masked_lm_labels.view(-1),
             ignore_index=-1,
         )
         if next_sentence_label is not None:
-            loss = loss + F.cross_entropy(
+            loss = loss + cross_entropy(
                 self.nsp(pooled).view(-1, 2).float(), next_sentence_label.view(-1)
             )
         return loss

@@ -17,7 +17,7 @@ import torch
 from . import models
 from .comm import Comm
 from .config import EngineConfig
-from .ops import hip_ctc
+from .ops import hip_ce, hip_ctc
 from .optimizer import DistributedOptimizer, FlatBertAdam, FlatSGD
 
 logger = logging.getLogger("oktopk_amd")
@@ -243,10 +243,10 @@ class Trainer:
         b = self.batches
         if b.family in ("cifar", "imagenet", "mnist"):
             out = self.model(b.x)
-            return torch.nn.functional.cross_entropy(out, b.y)
+            return hip_ce.cross_entropy(out, b.y)
         if b.family == "ptb":
             logits, _ = self.model(b.tokens)
-            return torch.nn.functional.cross_entropy(
+            return hip_ce.cross_entropy(
                 logits.view(-1, logits.size(-1)).float(), b.targets.view(-1)
             )
         if self.model_name == "lstman4":

@@ -30,6 +30,7 @@ setup(
                 "oktopk_amd/ops/csrc/attention_fa.hip",
                 "oktopk_amd/ops/csrc/lstm_cell.hip",
                 "oktopk_amd/ops/csrc/ctc_loss.hip",
+                "oktopk_amd/ops/csrc/cross_entropy.hip",
             ],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],

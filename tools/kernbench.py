@@ -238,6 +238,49 @@ def ctc_rows():
                             reps=20))
 
 
+def ce_rows():
+    """The MLM loss of BERT-base at bs 8, seq 128: bf16 logits [1024, 30522],
+    15 % of the rows labelled, the rest ignore_index = -1, forward + backward
+    to the logits.  F.cross_entropy (log_softmax, nll, fill, nll backward,
+    softmax backward) against ops.hip_ce.cross_entropy, eager and captured,
+    then each kernel alone.  GB/s counts what the kernel must move: forward
+    reads the labelled rows, backward reads them and writes every row."""
+    import torch.nn.functional as F
+
+    from oktopk_amd.ops.hip_ce import cross_entropy
+
+    os.environ["OKTOPK_HIP_CE"] = "1"
+    rows_, C = 1024, 30522
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn(rows_, C, generator=g).bfloat16().cuda().requires_grad_()
+    tgt = torch.randint(0, C, (rows_,), generator=g)
+    tgt[torch.rand(rows_, generator=g) >= 0.15] = -1
+    labelled = int((tgt >= 0).sum())
+    tgt = tgt.cuda()
+    xd = x.detach()
+    loss, stats, factor = H.ce_fwd(xd, tgt, -1, 1)
+    gout = torch.ones(1, device="cuda")
+    fwd_bytes = 2 * labelled * C
+    bwd_bytes = 2 * labelled * C + 2 * rows_ * C
+
+    torch_loss = lambda: torch.autograd.grad(F.cross_entropy(x, tgt, ignore_index=-1), x)
+    hip_loss = lambda: torch.autograd.grad(cross_entropy(x, tgt, ignore_index=-1), x)
+    print(f"# [{rows_}, {C}] bf16, {labelled} rows labelled")
+    print(f"{'op':44s} {'us':>9s} {'GB/s':>8s}")
+    for name, fn, nbytes, graph in (
+        ("F.cross_entropy fwd+bwd (eager)", torch_loss, None, False),
+        ("hip_ce.cross_entropy fwd+bwd (eager)", hip_loss, None, False),
+        ("F.cross_entropy fwd+bwd (graph)", torch_loss, None, True),
+        ("hip_ce.cross_entropy fwd+bwd (graph)", hip_loss, None, True),
+        ("ce_fwd + finalize (graph)", lambda: H.ce_fwd(xd, tgt, -1, 1), fwd_bytes, True),
+        ("ce_bwd (graph)", lambda: H.ce_bwd(xd, tgt, stats, factor, gout, -1),
+         bwd_bytes, True),
+    ):
+        sec = timeit_graph(fn, reps=20) if graph else timeit(fn, iters=50)
+        bw = f"{nbytes / GB / sec:8.0f}" if nbytes else f"{'':8s}"
+        print(f"{name:44s} {sec * 1e6:9.1f} {bw}", flush=True)
+
+
 def lstm_stack_rows():
     """The PTB word LM's two 1500-wide layers, T = 35, N = 20, forward +
     backward with an initial state and gradients at the final one: nn.LSTM
@@ -826,7 +869,7 @@ def main():
                          "row, default 15, for --only gauss, topk, "
                          "round2 and reduce)")
     ap.add_argument("--only", default="",
-                    choices=["", "colsum", "deferred", "residual_ln", "lstm", "ctc", "wire", "gauss", "sparse_step",
+                    choices=["", "colsum", "deferred", "residual_ln", "lstm", "ctc", "ce", "wire", "gauss", "sparse_step",
                              "topk", "round2", "reduce", "flat_sgd"],
                     help="run just one group of rows")
     args = ap.parse_args()
@@ -851,6 +894,9 @@ def main():
         return
     if args.only == "ctc":
         ctc_rows()
+        return
+    if args.only == "ce":
+        ce_rows()
         return
     if args.only == "wire":
         wire_rows(args.iters or 1000)
