@@ -14,6 +14,7 @@
 #include "cross_entropy.h"
 #include "ctc_loss.h"
 #include "grad_batch.h"
+#include "ln_param_grads.h"
 
 // launchers from kernels.hip
 extern "C" {
@@ -1081,6 +1082,75 @@ static int64_t small_grads_batched(
     return launches;
 }
 
+static bool ln_param_grads_deferrable(torch::Tensor gy, torch::Tensor x,
+                                      torch::Tensor mean, torch::Tensor rstd) {
+    // whether ln_param_grads_batched takes this site: contiguous bf16 gy / x
+    // of one shape [..., N], fp32 statistics of one value per row, and a row
+    // count whose summation order the kernel reproduces
+    if (!(gy.is_cuda() && gy.scalar_type() == torch::kBFloat16 &&
+          gy.is_contiguous() && gy.dim() >= 1 && gy.numel() > 0 &&
+          x.scalar_type() == torch::kBFloat16 && x.is_contiguous() &&
+          x.device() == gy.device() && x.sizes() == gy.sizes()))
+        return false;
+    const int64_t N = gy.size(-1), M = gy.numel() / N;
+    for (const torch::Tensor* st : {&mean, &rstd}) {
+        if (!(st->scalar_type() == torch::kFloat32 && st->is_contiguous() &&
+              st->device() == gy.device() && st->numel() == M))
+            return false;
+    }
+    return ln_param_grads_shape_ok(M, N) != 0;
+}
+
+static int64_t ln_param_grads_batched(
+        std::vector<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor,
+                               torch::Tensor, torch::Tensor, torch::Tensor>> entries) {
+    // One launch per LN_GRAD_BATCH_CAPACITY entries
+    // (gy, x, mean, rstd, dst_gamma, dst_beta): dst_gamma += gamma gradient,
+    // dst_beta += beta gradient, the bits of native_layer_norm_backward
+    // followed by dst.add_(g).  Every entry must be ln_param_grads_deferrable;
+    // dst_* are contiguous bf16 [N] at any element offset, and no two
+    // destinations of one call may share elements.  Returns the number of
+    // launches.
+    std::vector<LnGradItem> items;
+    items.reserve(entries.size());
+    c10::optional<c10::Device> dev;
+    for (auto& [gy, x, mean, rstd, dst_gamma, dst_beta] : entries) {
+        TORCH_CHECK(ln_param_grads_deferrable(gy, x, mean, rstd),
+                    "ln_param_grads_batched: an entry is outside the supported "
+                    "range (contiguous cuda bf16 gy / x, fp32 mean / rstd, "
+                    "128 <= rows <= 1024); nothing was launched");
+        const int64_t N = gy.size(-1);
+        for (const torch::Tensor* dst : {&dst_gamma, &dst_beta}) {
+            TORCH_CHECK(dst->is_cuda() && dst->scalar_type() == torch::kBFloat16 &&
+                        dst->is_contiguous() && dst->numel() == N &&
+                        dst->device() == gy.device(),
+                        "ln_param_grads_batched: dst must be contiguous cuda "
+                        "bf16 [N] on gy's device");
+        }
+        if (!dev.has_value()) dev = gy.device();
+        TORCH_CHECK(gy.device() == *dev,
+                    "ln_param_grads_batched: all entries on one device");
+        LnGradItem it{};
+        it.gy = gy.data_ptr();
+        it.x = x.data_ptr();
+        it.mean = mean.data_ptr<float>();
+        it.rstd = rstd.data_ptr<float>();
+        it.dst_gamma = dst_gamma.data_ptr();
+        it.dst_beta = dst_beta.data_ptr();
+        it.M = gy.numel() / N;
+        it.N = N;
+        items.push_back(it);
+    }
+    if (items.empty()) return 0;
+    const at::cuda::CUDAGuard guard(*dev);
+    const int launches = launch_ln_param_grads_bf16(items.data(), (int)items.size(),
+                                                    cur_stream());
+    TORCH_CHECK(launches >= 0,
+                "ln_param_grads_batched: an entry does not fit the kernel; "
+                "nothing was launched");
+    return launches;
+}
+
 static torch::Tensor linear_bwd_into(torch::Tensor gy, torch::Tensor x,
                                      torch::Tensor w,
                                      c10::optional<torch::Tensor> gw_dst,
@@ -2137,6 +2207,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "(src, dst, is_colsum); returns the number of launches",
           py::arg("entries"));
     m.attr("GRAD_BATCH_CAPACITY") = (int64_t)GRAD_BATCH_CAPACITY;
+    m.def("ln_param_grads_deferrable", &ln_param_grads_deferrable,
+          "whether ln_param_grads_batched takes a site (gy, x, mean, rstd)");
+    m.def("ln_param_grads_batched", &ln_param_grads_batched,
+          "batched LayerNorm gamma / beta gradients added onto their slots: a "
+          "list of (gy, x, mean, rstd, dst_gamma, dst_beta); returns the "
+          "number of launches",
+          py::arg("entries"));
     m.def("ln_bwd_supported", &ln_bwd_into_supported,
           "hidden sizes ln_bwd_into handles");
     m.def("ln_bwd_into", &ln_bwd_into,

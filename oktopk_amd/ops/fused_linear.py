@@ -76,6 +76,34 @@ def defer_small_grads_enabled() -> bool:
     return os.environ.get("OKTOPK_DEFER_SMALL_GRADS", "1") != "0"
 
 
+def batch_ln_grads_enabled() -> bool:
+    """The LayerNorm gamma / beta gradients of a backward pass are computed in
+    one launch at its end (ops/csrc/ln_param_grads.hip, torch's bits;
+    profiles/README.md r21).  OKTOPK_BATCH_LN_GRADS=0 restores torch's two
+    kernels per site followed by the batched add."""
+    return os.environ.get("OKTOPK_BATCH_LN_GRADS", "1") != "0"
+
+
+class LnGradSource:
+    """What a pending LayerNorm entry holds in place of a gradient: the
+    tensors the gamma / beta gradients of one site are computed from.  The
+    gamma and the beta entry of a site share one of these."""
+
+    def __init__(self, gy, x, mean, rstd, w, b, w_dst, b_dst):
+        self.gy, self.x, self.mean, self.rstd = gy, x, mean, rstd
+        self.w, self.b, self.w_dst, self.b_dst = w, b, w_dst, b_dst
+        self.device = gy.device
+
+    def materialise(self):
+        """(gw, gb) by torch's own kernels: the bits the batched launch adds."""
+        H = self.x.shape[-1]
+        stat_shape = self.x.shape[:-1] + (1,)
+        _, gw, gb = torch.ops.aten.native_layer_norm_backward(
+            self.gy, self.x, [H], self.mean.view(stat_shape),
+            self.rstd.view(stat_shape), self.w, self.b, [False, True, True])
+        return gw, gb
+
+
 class GradSlotOwner:
     """Per-optimizer state the nodes share: ids of the parameters whose slot
     was written since the last zero_grad(), and the small gradient writes of
@@ -87,14 +115,22 @@ class GradSlotOwner:
     GRAD_BATCH_CAPACITY entries (ops/csrc/direct_grad.hip) runs when the
     backward pass ends, from the autograd engine's end-of-backward callback,
     on the stream the nodes ran on.  The bits are those of the immediate
-    launches; only their time and number change.  Rules:
+    launches; only their time and number change.  Unless
+    OKTOPK_BATCH_LN_GRADS=0, a LayerNorm site of a supported shape defers the
+    reductions themselves: its two entries hold one LnGradSource in place of
+    the gradients, and the flush hands those sites to a second batched launch
+    (ops/csrc/ln_param_grads.hip) that computes torch's gamma / beta
+    gradients and adds them onto the slots.  Rules:
       * `written` is updated when a write is deferred, as if it had run;
       * a node that finds a pending entry for its parameter (a module used
         twice in one backward) flushes before an accumulating bias write,
         and folds a further LayerNorm gradient into the pending one with a
-        bf16 add, which is what autograd's input buffer does;
+        bf16 add, which is what autograd's input buffer does; a pending
+        LnGradSource is first turned into its two gradients by torch's own
+        kernels;
       * the list holds its sources alive (the gy of every Linear, ~230 MB at
-        the BERT-base bench shape) until the flush drops them;
+        the BERT-base bench shape, and gy, x and the row statistics of every
+        LnGradSource, ~82 MB more) until the flush drops them;
       * discard() forgets entries a failed backward left behind."""
 
     def __init__(self):
@@ -112,6 +148,8 @@ class GradSlotOwner:
         if at is not None:
             # add entries only: callers flush before a second colsum write
             assert not is_colsum and not self.pending[at][2]
+            if isinstance(self.pending[at][0], LnGradSource):
+                self._materialise(self.pending[at][0])
             self.pending[at] = (self.pending[at][0] + src, dst, False)
             return
         self._pending_at[id(p)] = len(self.pending)
@@ -121,6 +159,18 @@ class GradSlotOwner:
             torch.autograd.Variable._execution_engine.queue_callback(self.flush)
             self._callback_queued = True
 
+    def defer_ln(self, site: LnGradSource) -> None:
+        """The gamma and beta gradients of one site, still to be computed.
+        Only for parameters without a pending entry."""
+        assert not self.has_pending(site.w) and not self.has_pending(site.b)
+        self.defer(site.w, site, site.w_dst, False)
+        self.defer(site.b, site, site.b_dst, False)
+
+    def _materialise(self, site: LnGradSource) -> None:
+        gw, gb = site.materialise()
+        self.pending[self._pending_at[id(site.w)]] = (gw, site.w_dst, False)
+        self.pending[self._pending_at[id(site.b)]] = (gb, site.b_dst, False)
+
     def flush(self) -> None:
         self._callback_queued = False
         if not self.pending:
@@ -129,8 +179,15 @@ class GradSlotOwner:
 
         entries, stream = self.pending, self._stream
         self.pending, self._pending_at, self._stream = [], {}, None
+        plain = [e for e in entries if not isinstance(e[0], LnGradSource)]
+        # a site once, at its gamma entry
+        sites = [(s.gy, s.x, s.mean, s.rstd, s.w_dst, s.b_dst)
+                 for s, dst, _ in entries
+                 if isinstance(s, LnGradSource) and dst is s.w_dst]
         with torch.cuda.stream(stream):
-            _hip_ops.small_grads_batched(entries)
+            _hip_ops.small_grads_batched(plain)
+            if sites:
+                _hip_ops.ln_param_grads_batched(sites)
 
     def discard(self) -> None:
         self.pending, self._pending_at, self._stream = [], {}, None

@@ -813,6 +813,46 @@ def slot_add_bf16(dst: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     return (dst.float() + g.float()).to(torch.bfloat16)
 
 
+def ln_param_grads_torch_order(gy: torch.Tensor, x: torch.Tensor,
+                               mean: torch.Tensor, rstd: torch.Tensor):
+    """(gamma gradient, beta gradient) of a LayerNorm over the last dimension
+    of x [M, N], as bf16 [N], summed in the order of torch's ROCm kernels
+    cuComputePartGradGammaBeta and cuComputeGradGammaBeta for bf16 inputs
+    with 128 <= M <= 1024: the association tree native ln_param_grads_batched
+    reproduces before it adds onto the slots (slot_add_bf16).
+
+    Per column, with t[r] = (gy[r] * (x[r] - mean[r])) * rstd[r] for gamma and
+    t[r] = gy[r] for beta, all in plain fp32 and every sum started at +0:
+      * chunk p (p < 64) is rows 16p .. 16p + 15, rows at or past M being +0;
+        A(j) = ((t[j] + t[j+4]) + t[j+8]) + t[j+12] inside it, j < 4, and
+        P(p) = (A(0) + A(2)) + (A(1) + A(3));
+      * S(j) = P(8j) + P(8j+1) + ... + P(8j+7) left to right, j < 8, then
+        S[j] += S[j + off] for off = 4, 2, 1;
+      * S(0) is rounded once to bf16."""
+    M, N = gy.shape
+    assert x.shape == gy.shape and 128 <= M <= 1024
+    dy = gy.detach().float().cpu()
+    mu = mean.detach().float().cpu().reshape(M, 1)
+    rs = rstd.detach().float().cpu().reshape(M, 1)
+    terms = ((dy * (x.detach().float().cpu() - mu)) * rs, dy)
+    out = []
+    for t in terms:
+        rows = torch.zeros(1024, N, dtype=torch.float32)
+        rows[:M] = t
+        chunk = rows.view(64, 4, 4, N)          # row = 16 p + 4 k + j
+        a = torch.zeros(64, 4, N, dtype=torch.float32)
+        for k in range(4):
+            a = a + chunk[:, k]
+        p = ((a[:, 0] + a[:, 2]) + (a[:, 1] + a[:, 3])).view(8, 8, N)
+        s = torch.zeros(8, N, dtype=torch.float32)
+        for i in range(8):
+            s = s + p[:, i]
+        for off in (4, 2, 1):
+            s = s[:off] + s[off:2 * off]
+        out.append(s[0].to(torch.bfloat16))
+    return out[0], out[1]
+
+
 # -- flash attention --------------------------------------------------------
 # Two references of the op of ops/csrc/attention_fa.hip over the packed bf16
 # projection buffer qkv [b, s, 3*nh*64]: ctx = (softmax(QK^T/8 + mask) *

@@ -6,8 +6,10 @@ launch for the residual add, the row moments and the normalisation, in place
 of torch's add, RowwiseMomentsCUDAKernel and LayerNormForwardCUDAKernel.
 Backward: one launch for the LayerNorm input gradient and the dropout
 backward, in place of layer_norm_grad_input_kernel and masked_scale_kernel;
-the gamma / beta gradients stay torch's native_layer_norm_backward and go to
-the deferred add slots exactly as in slot_ln.py.
+the gamma / beta gradients are those of torch's native_layer_norm_backward,
+computed by the batched launch at the end of the pass that leaves the same
+bits (by torch itself with OKTOPK_BATCH_LN_GRADS=0 or an unsupported row
+count), and go to the deferred add slots exactly as in slot_ln.py.
 
 A site's output feeds the next sub-layer's GEMM and the next residual add, and
 autograd would add the two incoming gradients with a kernel of its own.  The
@@ -37,7 +39,7 @@ import os
 import torch
 
 from .fused_linear import _ADD_SLOT_ATTR
-from .slot_ln import defer_ln_param_grads
+from .slot_ln import defer_ln_param_grad_sums, defer_ln_param_grads
 
 
 def residual_ln_enabled() -> bool:
@@ -109,7 +111,9 @@ class _ResidualLayerNormFn(torch.autograd.Function):
         gy, gs, ga = _hip_ops.residual_ln_bwd(gy1, gy2, s, mean, rstd, w, mask,
                                               ctx.scale)
         gw = gb = None
-        if need[2] or need[3]:
+        if need[2] and need[3] and defer_ln_param_grad_sums(w, b, gy, s, mean, rstd):
+            pass
+        elif need[2] or need[3]:
             stat_shape = s.shape[:-1] + (1,)
             _, gw, gb = torch.ops.aten.native_layer_norm_backward(
                 gy, s, [H], mean.view(stat_shape), rstd.view(stat_shape), w, b,

@@ -18,7 +18,11 @@ Without that opt-in, an optimizer that defers small gradient writes
 beta as add slots.  The node then runs torch's own
 native_layer_norm_backward for all three gradients, so every bit is torch's,
 hands autograd no gamma / beta gradient, and leaves the two `slot += g` adds
-to the batched launch at the end of the backward pass.
+to the batched launch at the end of the backward pass.  With 128 to 1024
+rows (and not OKTOPK_BATCH_LN_GRADS=0) the node calls torch for the input
+gradient only: the gamma / beta reductions wait for the end of the pass
+too, where one launch (ops/csrc/ln_param_grads.hip) computes them for every
+site in torch's summation order and adds them onto the slots.
 """
 from __future__ import annotations
 
@@ -26,28 +30,57 @@ import os
 
 import torch
 
-from .fused_linear import (_ADD_SLOT_ATTR, _SLOT_ATTR, _bound_slot,
-                           defer_small_grads_enabled)
+from .fused_linear import (_ADD_SLOT_ATTR, _SLOT_ATTR, LnGradSource, _bound_slot,
+                           batch_ln_grads_enabled, defer_small_grads_enabled)
 
 
 def direct_ln_enabled() -> bool:
     return os.environ.get("OKTOPK_DIRECT_LN", "0") == "1"
 
 
+def _add_slots(w, b):
+    """(gamma slot, beta slot, owner) when both are bound as add slots of one
+    owner and deferral is on, else None."""
+    if not defer_small_grads_enabled():
+        return None
+    was, bas = _bound_slot(w, _ADD_SLOT_ATTR), _bound_slot(b, _ADD_SLOT_ATTR)
+    if was is None or bas is None or was[1] is not bas[1]:
+        return None
+    return was[0], bas[0], was[1]
+
+
 def defer_ln_param_grads(w, b, gw, gb) -> bool:
     """Hand torch's gamma / beta gradients to the parameters' add slots, to be
     added by the batched launch at the end of backward.  False: not bound as
     add slots of one owner (or deferral is off); return them to autograd."""
-    if not defer_small_grads_enabled():
-        return False
-    was, bas = _bound_slot(w, _ADD_SLOT_ATTR), _bound_slot(b, _ADD_SLOT_ATTR)
-    if (was is not None and bas is not None and was[1] is bas[1]
+    slots = _add_slots(w, b)
+    if (slots is not None
             and gw.dtype == torch.bfloat16 and gb.dtype == torch.bfloat16
             and gw.is_contiguous() and gb.is_contiguous()):
-        was[1].defer(w, gw, was[0], False)
-        bas[1].defer(b, gb, bas[0], False)
+        slots[2].defer(w, gw, slots[0], False)
+        slots[2].defer(b, gb, slots[1], False)
         return True
     return False
+
+
+def defer_ln_param_grad_sums(w, b, gy, x, mean, rstd) -> bool:
+    """Leave the gamma / beta gradients of this site to the batched launch at
+    the end of backward, which computes them with torch's bits and adds them
+    onto the slots (OKTOPK_BATCH_LN_GRADS).  False: the switch is off, the
+    parameters are not add slots of one owner, the shape is outside what the
+    kernel reproduces, or a parameter already has a pending entry (a module
+    used twice); the caller then computes them with torch, as before."""
+    if not batch_ln_grads_enabled():
+        return False
+    slots = _add_slots(w, b)
+    if slots is None or slots[2].has_pending(w) or slots[2].has_pending(b):
+        return False
+    from oktopk_amd import _hip_ops
+
+    if not _hip_ops.ln_param_grads_deferrable(gy, x, mean, rstd):
+        return False
+    slots[2].defer_ln(LnGradSource(gy, x, mean, rstd, w, b, slots[0], slots[1]))
+    return True
 
 
 class _SlotLayerNormFn(torch.autograd.Function):
@@ -75,8 +108,15 @@ class _SlotLayerNormFn(torch.autograd.Function):
                 gx = _hip_ops.ln_bwd_into(gy, x, w, mean, rstd, ws[0], bs[0], w_acc)
                 owner.written.update((id(w), id(b)))
                 return gx, None, None, None
+        gy = gy.contiguous()
+        if need[1] and need[2] and defer_ln_param_grad_sums(w, b, gy, x, mean, rstd):
+            gx = None
+            if need[0]:
+                gx = torch.ops.aten.native_layer_norm_backward(
+                    gy, x, [H], mean, rstd, w, b, [True, False, False])[0]
+            return gx, None, None, None
         gx, gw, gb = torch.ops.aten.native_layer_norm_backward(
-            gy.contiguous(), x, [H], mean, rstd, w, b,
+            gy, x, [H], mean, rstd, w, b,
             [bool(need[0]), bool(need[1]), bool(need[2])])
         if need[1] and need[2] and defer_ln_param_grads(w, b, gw, gb):
             return gx, None, None, None

@@ -25,6 +25,7 @@ setup(
                 "oktopk_amd/ops/csrc/round2_tail.hip",
                 "oktopk_amd/ops/csrc/reduce_merge.hip",
                 "oktopk_amd/ops/csrc/direct_grad.hip",
+                "oktopk_amd/ops/csrc/ln_param_grads.hip",
                 "oktopk_amd/ops/csrc/ln_bwd.hip",
                 "oktopk_amd/ops/csrc/residual_ln.hip",
                 "oktopk_amd/ops/csrc/attention_fa.hip",

@@ -115,6 +115,44 @@ def deferred_rows():
     return rows
 
 
+def ln_param_grads_rows():
+    """The LayerNorm gamma / beta gradients of one BERT-base backward (bs 8,
+    seq 128): 26 sites of [1024, 768], torch's two kernels a site
+    (native_layer_norm_backward, 52 launches) followed by the batched slot
+    adds, against one ln_param_grads_batched call.  Every site has tensors of
+    its own, as in the backward pass; GB/s counts gy, x and the row
+    statistics of every site."""
+    g = torch.Generator().manual_seed(5)
+    R, C, sites = 1024, 768, 26
+    entries, torch_args = [], []
+    for _ in range(sites):
+        gy = torch.randn(R, C, generator=g).bfloat16().cuda()
+        x = torch.randn(R, C, generator=g).bfloat16().cuda()
+        w, b = (torch.randn(C, generator=g).bfloat16().cuda() for _ in range(2))
+        _, mean, rstd = torch.native_layer_norm(x, (C,), w, b, 1e-12)
+        slots = torch.zeros(2 * C + 16, dtype=torch.bfloat16, device="cuda")
+        dg, db = slots[3:3 + C], slots[C + 9:2 * C + 9]
+        assert H.ln_param_grads_deferrable(gy, x, mean, rstd)
+        entries.append((gy, x, mean, rstd, dg, db))
+        torch_args.append((gy, x, [C], mean, rstd, w, b, [False, True, True]))
+    nbytes = sites * (2 * 2 * R * C + 2 * 4 * R)
+
+    def torch_pair():
+        adds = []
+        for args, e in zip(torch_args, entries):
+            _, gw, gb = torch.ops.aten.native_layer_norm_backward(*args)
+            adds += [(gw, e[4], False), (gb, e[5], False)]
+        H.small_grads_batched(adds)
+
+    rows = []
+    for name, fn in (("torch gamma/beta pairs + adds (53 launches)", torch_pair),
+                     ("ln_param_grads_batched (1 launch)",
+                      lambda: H.ln_param_grads_batched(entries))):
+        ms = timeit_graph(fn, reps=10) * 1000
+        rows.append((name, ms, nbytes / GB / (ms / 1000)))
+    return rows
+
+
 def residual_ln_rows():
     """One post-LN residual site of BERT-base (1024 rows, H 768, dropout 0.1):
     the forward chain after torch's dropout (add, row moments, normalise) and
@@ -869,7 +907,7 @@ def main():
                          "row, default 15, for --only gauss, topk, "
                          "round2 and reduce)")
     ap.add_argument("--only", default="",
-                    choices=["", "colsum", "deferred", "residual_ln", "lstm", "ctc", "ce", "wire", "gauss", "sparse_step",
+                    choices=["", "colsum", "deferred", "ln_param_grads", "residual_ln", "lstm", "ctc", "ce", "wire", "gauss", "sparse_step",
                              "topk", "round2", "reduce", "flat_sgd"],
                     help="run just one group of rows")
     args = ap.parse_args()
@@ -885,6 +923,9 @@ def main():
         return
     if args.only == "deferred":
         print_rows(deferred_rows())
+        return
+    if args.only == "ln_param_grads":
+        print_rows(ln_param_grads_rows())
         return
     if args.only == "residual_ln":
         print_rows(residual_ln_rows())
