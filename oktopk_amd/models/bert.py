@@ -83,7 +83,8 @@ class BertSelfAttention(nn.Module):
         b, s, h = x.shape
         qkv_flat = self.qkv(x)
         # hand-written CDNA4 fused attention (QK^T+softmax+dropout+PV in one
-        # MFMA kernel) on GPU/bf16 at the reference shape; eager otherwise
+        # MFMA kernel) on GPU/bf16 at seq % 128 == 0, and at any seq with
+        # OKTOPK_FA_ANY_SEQ=1; eager otherwise
         from ..ops.fused_attn import fused_attention, fused_attn_available
 
         if fused_attn_available(qkv_flat, self.nh, s, self.attn_drop.p):

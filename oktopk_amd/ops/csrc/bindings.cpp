@@ -1986,8 +1986,9 @@ static std::vector<torch::Tensor> attn_fwd_fa(torch::Tensor qkv,
     int64_t H3 = qkv.size(2);
     int64_t H = H3 / 3;
     int64_t HD = H / num_heads;
-    TORCH_CHECK(S % 128 == 0 && HD == 64,
-                "flash attention needs seq % 128 == 0 and hd == 64");
+    // seq % 128 == 0 launches the dense kernels, any other the ragged ones
+    TORCH_CHECK(S >= 1 && HD == 64,
+                "flash attention needs seq >= 1 and hd == 64");
     const at::cuda::CUDAGuard guard(qkv.device());
     auto out = torch::empty({B, S, H}, qkv.options());
     torch::Tensor lse;
@@ -2015,7 +2016,9 @@ static std::vector<torch::Tensor> attn_fwd_fa(torch::Tensor qkv,
         at::PhiloxCudaState state;
         {
             std::lock_guard<std::mutex> lock(gen->mutex_);
-            state = gen->philox_cuda_state((B * num_heads * S * S + 3) / 4 + 1);
+            // one counter per (bh, query-row quad, key): ceil(S/4) quads
+            state = gen->philox_cuda_state(
+                B * num_heads * ((S + 3) / 4) * S + 1);
         }
         if (state.captured_) {
             captured = 1;
@@ -2058,8 +2061,12 @@ static torch::Tensor attn_bwd_fa(torch::Tensor qkv, torch::Tensor go,
     int64_t B = qkv.size(0), S = qkv.size(1);
     int64_t H = qkv.size(2) / 3;
     int64_t HD = H / num_heads;
-    TORCH_CHECK(S % 128 == 0 && HD == 64,
-                "flash attention bwd needs seq % 128 == 0 and hd == 64");
+    TORCH_CHECK(S >= 1 && HD == 64,
+                "flash attention bwd needs seq >= 1 and hd == 64");
+    TORCH_CHECK(go.is_cuda() && lse.is_cuda() && dvec.is_cuda() &&
+                go.numel() == B * S * H && lse.numel() == B * num_heads * S &&
+                dvec.numel() == B * num_heads * S,
+                "go / lse / dvec do not match qkv");
     const at::cuda::CUDAGuard guard(qkv.device());
     auto dqkv = torch::empty_like(qkv);
     const void* mptr = nullptr;
@@ -2087,8 +2094,8 @@ static void dropout_mask_mul_(torch::Tensor a, torch::Tensor philox_state,
                               double dropout_p) {
     TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16 &&
                 a.is_contiguous());
-    TORCH_CHECK(a.dim() == 3 && a.size(1) == a.size(2) &&
-                a.size(1) % 4 == 0, "a must be [BH, S, S]");
+    TORCH_CHECK(a.dim() == 3 && a.size(1) == a.size(2) && a.size(1) >= 1,
+                "a must be [BH, S, S]");
     TORCH_CHECK(philox_state.numel() == 6);
     auto st = philox_state.to(torch::kCPU);
     auto* p = st.data_ptr<int64_t>();
@@ -2231,14 +2238,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("sumsq_into_", &sumsq_into_,
           "accumulate sum(t^2) into a device fp64[1] (no host sync)");
     m.def("attn_fwd_fa", &attn_fwd_fa,
-          "flash (online-softmax) attention forward: any seq % 128 == 0, "
+          "flash (online-softmax) attention forward: any seq >= 1 (dense "
+          "kernels at seq % 128 == 0, ragged ones otherwise), "
           "hd=64 bf16; returns (ctx, lse, philox_state) — O(S) memory");
     m.def("attn_bwd_fa", &attn_bwd_fa,
           "flash attention backward: dQ/dK/dV from (qkv, gO, lse, D) with "
-          "philox dropout-mask regeneration — nothing O(S^2) materialised");
+          "philox dropout-mask regeneration — nothing O(S^2) materialised; "
+          "any seq >= 1");
     m.def("dropout_mask_mul_", &dropout_mask_mul_,
-          "regenerate the forward's philox dropout mask in-place: "
-          "a[i] = keep ? a[i]/keep_prob : 0");
+          "regenerate the forward's philox dropout mask in-place on "
+          "a [BH, S, S], any S: a[i] = keep ? a[i]/keep_prob : 0");
     m.def("wire_max_segments", []() { return (int64_t)wire_max_segments(); },
           "largest segment count the wire codec kernels take");
     m.def("pack_regions", &pack_regions,

@@ -1,6 +1,8 @@
 """Fused self-attention with autograd — the production path since round 2.
 
-_FlashAttention (default, any seq % 128 == 0 / hd 64): online-softmax
+_FlashAttention (default at any seq % 128 == 0 / hd 64; at every other
+seq >= 1 with the opt-in OKTOPK_FA_ANY_SEQ=1, which selects the kernels'
+ragged instantiations): online-softmax
 forward (ops/csrc/attention_fa.hip) saving only ctx + per-row LSE, and a
 hand-written two-kernel backward (query-parallel dQ; key-parallel dK/dV)
 that recomputes P from the LSE and REGENERATES the philox dropout mask —
@@ -25,12 +27,16 @@ def fused_attn_available(x: torch.Tensor, num_heads: int, seq: int, dropout_p: f
     # shape: bert_base 10.30 -> 9.99 (s128), 12.77 -> 11.87 (s256),
     # 17.0 -> 16.1 (s512); bert_large s512 35.7 -> 34.3 (2-rep A/Bs,
     # profiles/README.md r02).  OKTOPK_FUSED_ATTN=0 forces SDPA.
+    # OKTOPK_FA_ANY_SEQ=1 (opt-in, read per call) also accepts every other
+    # seq >= 1: the ragged instantiations of the same three kernels.
     if os.environ.get("OKTOPK_FUSED_ATTN", "") == "0":
         return False
     if not (x.is_cuda and x.dtype == torch.bfloat16):
         return False
     hd = x.shape[-1] // (3 * num_heads)
-    if seq % 128 != 0 or hd != 64:
+    if hd != 64 or seq < 1:
+        return False
+    if seq % 128 != 0 and os.environ.get("OKTOPK_FA_ANY_SEQ", "") != "1":
         return False
     from . import hip_available
 
@@ -38,7 +44,8 @@ def fused_attn_available(x: torch.Tensor, num_heads: int, seq: int, dropout_p: f
 
 
 class _FlashAttention(torch.autograd.Function):
-    """Online-softmax forward (any seq % 128 == 0): the kernel materialises
+    """Online-softmax forward (any seq >= 1; fused_attn_available decides
+    which lengths the model sends here): the kernel materialises
     nothing O(S^2) — only ctx and the per-row LSE come back.  Backward
     recomputes P = exp(QK^T*scale + mask - lse) (already normalised, no
     softmax pass) and REGENERATES the dropout mask from the same philox
@@ -136,5 +143,6 @@ class _FlashAttention(torch.autograd.Function):
 def fused_attention(qkv, mask, num_heads, dropout_p, training):
     """ctx = dropout(softmax(QK^T*scale + mask)) @ V from the fused qkv
     projection buffer [b, s, 3h]; returns [b, s, h]: the flash
-    (online-softmax) kernel, any seq % 128 == 0."""
+    (online-softmax) kernel, any seq >= 1 (ragged kernels when
+    seq % 128 != 0)."""
     return _FlashAttention.apply(qkv, mask, num_heads, dropout_p, training)
